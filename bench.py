@@ -6,11 +6,13 @@ trainable weights (the 397.6 M `temporal_transformer_block` parameters of train_
 N=1: BASELINE.json configs[1] -- SVD UNet (1,524,623,082 params), 14 frames, 512x320 (latent 64x40), fp16,
 batch 1, random-init weights, synthetic latents already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see the driver contract).  Extra objects:
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times the K steps and reports them; with
+--dump-outputs DIR it also writes what the last timed step computed (dump_outputs).  The extra objects below, the clock sampler and, with
+N > 1, the gradient exchange timed on its own are measured with --full only (null otherwise):
   roofline     -- the dominant kernel family (MFMA GEMM / implicit convolution / weight gradient): algorithmic FLOPs of all its launches in
                   one step / their summed duration.  Clock at one rank under hipGraph: device timestamps written by one-lane `svdx_stamp`
                   kernels around every launch inside a second capture of the step (replay conditions; `clock` says so); otherwise HIP
@@ -160,6 +162,28 @@ def make_batch(B, T, h, w, cross_dim, seed, dev):
     ids = torch.tensor([[7.0, 127.0, float(cond_sigma[0])]]).repeat(B, 1)     # train_svd.py:981-988
     return dict(unet_in=unet_in.to(dev), timesteps=ts.to(dev), ehs=ehs.to(dev), added_time_ids=ids.to(dev),
                 noisy_latents=noisy.to(dev), target=latents.to(dev), sigmas=sigmas.to(dev))
+
+
+DUMP_SAMPLE = 1 << 21      # positions kept of each flat buffer: 4 x 8 MB of float32, well under the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, trainer):
+    """What the timed step hands its caller, as of the last timed step: the loss (mean over ranks and micro-batches), the optimizer
+    state (step count, loss scale, ...) and the flat fp32 buffers every trainable parameter and its .grad are views of -- updated
+    weights, gradients, both AdamW moments.  At the benched shape those hold 397.6 M elements each, so each is sampled at the same
+    DUMP_SAMPLE positions, drawn from a fixed seed: the same arguments give the same positions on every run and every build."""
+    import numpy as np
+    n = trainer.n_flat
+    if n <= DUMP_SAMPLE:
+        idx = torch.arange(n)
+    else:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(2024)).sort().values
+    idx = idx.to(trainer.dev)
+    arrays = {"loss": trainer.last_loss().reshape(1), "opt_state": trainer.opt_state, "params": trainer.p_flat[idx],
+              "grads": trainer.g_flat[idx], "exp_avg": trainer.m_flat[idx], "exp_avg_sq": trainer.v_flat[idx]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def cpu_baseline(dev=None, dtype=torch.float16, c2=True):
@@ -415,12 +439,22 @@ def main():
     ap.add_argument("--launch-log", default=None,
                     help="developer aid: write the ordered list of libsvdx calls of ONE eager step (entry name + scalar arguments) to this "
                          "JSON file; tools/step_trace.py joins it with a rocprofv3 kernel trace of the graph-replayed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: roofline, CPU baseline, real loop, shader "
+                         "clock / power during the timed steps and, with N > 1, the gradient exchange on its own (each --no-* option still "
+                         "drops its leg)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.gemm_table and not args.full:
+        ap.error("--gemm-table comes from the roofline leg: add --full")
     if args.no_overlap:
         args.overlap = "single"
     if args.overlap == "vae":
         args.with_vae = True
-    if args.gpus > 1 and "NCCL_DEBUG" not in os.environ:
+    if args.gpus > 1 and args.full and "NCCL_DEBUG" not in os.environ:
         # what RCCL decided (rings / trees, channels, algorithm and protocol per size) goes to a per-process file, never to stdout
         os.environ.update(NCCL_DEBUG="INFO", NCCL_DEBUG_SUBSYS="INIT,GRAPH,TUNING", NCCL_DEBUG_FILE="/tmp/svdx_rccl_%h_%p.log")
 
@@ -587,7 +621,7 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    sampler = ClockSampler(local_rank) if rank == 0 and os.environ.get("SVDX_NO_CLOCK_SAMPLER") != "1" else None
+    sampler = ClockSampler(local_rank) if args.full and rank == 0 and os.environ.get("SVDX_NO_CLOCK_SAMPLER") != "1" else None
     trainer.exposed_events = [] if world > 1 else None     # two event records per step: what of the collective nothing hid
     t0 = time.perf_counter()
     if sampler is not None:
@@ -611,6 +645,8 @@ def main():
     state = trainer.opt_state.cpu().tolist()
     ms = elapsed / args.steps * 1e3
     value = world * B * args.grad_accum * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer)      # before anything below steps the trainer again
 
     # ---- the same step with the VAE encode of the NEXT micro-batch running beside it (train_svd.py:948, 957-960) ----------------
     vae_info = None
@@ -674,7 +710,7 @@ def main():
 
     # ---- the step as a training loop runs it ------------------------------------------------------------------------------------
     real = None
-    if not args.no_real_loop:
+    if args.full and not args.no_real_loop:
         try:
             real = real_loop_leg(args, trainer, dev, dt, world, rank, T)
         except Exception as e:  # noqa: BLE001
@@ -684,8 +720,8 @@ def main():
         torch.cuda.synchronize()
 
     # ---- what RCCL saw: ranks (an all-reduce of ones) and the cost of the gradient exchange on its own -------------------------
-    ranks_seen, allreduce_ms, direct_ms, rccl = 1, None, None, None
-    if world > 1:
+    ranks_seen, allreduce_ms, direct_ms, rccl = (1 if world == 1 else None), None, None, None
+    if world > 1 and args.full:
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)
         ranks_seen = int(ones.item())
@@ -743,7 +779,7 @@ def main():
     roof = None
     # Every rank runs the instrumented step (same collectives on all ranks -- a rank-0-only step would leave its all-reduces without
     # peers); only rank 0 installs the timing hooks and reports.
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         k = trainer.rt.k
         orig, orig_tn = k.gemm, k.gemm_tn
         recs, recs_bytes = [], []
@@ -992,7 +1028,7 @@ def main():
                     "temporal_self_attention": tsa_op}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(dev, dt, c2=not args.no_cpu_c2 and not args.tiny)
         except Exception as e:  # noqa: BLE001

@@ -3,7 +3,7 @@ cost model's (split, tile) choice, the workgroups it launches, how many rounds t
 the two-stage four-wave tiles that fit twice on a CU), the share of the slots the last round fills and the share of a tile that is
 padding -- sorted by the time that quantisation costs.  This is the table the 192-row and 96-row tiles of round 3 came from.
 
-    python bench.py --gemm-table --steps 20 --no-cpu-baseline      (on the GPU box; writes gpurun_out/gemm_table.json)
+    python bench.py --full --gemm-table --steps 20 --no-cpu-baseline      (on an MI355X; writes the table read below)
     python tools/fill_table.py [gpurun_out/gemm_table.json]
 """
 import json
@@ -28,7 +28,7 @@ def main():
         import re
         traces = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_step_trace.txt")))
         if not traces:
-            raise SystemExit(f"{path} not found and no profiles/r*_step_trace.txt: run `python bench.py --gemm-table --steps 20 --no-cpu-baseline` on the GPU box")
+            raise SystemExit(f"{path} not found and no profiles/r*_step_trace.txt: run `python bench.py --full --gemm-table --steps 20 --no-cpu-baseline` on an MI355X")
         path = traces[-1]
         print(f"# reading {os.path.relpath(path, ROOT)} (no gpurun_out/gemm_table.json here)")
         table = []

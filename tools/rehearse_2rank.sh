@@ -5,7 +5,7 @@
 out=$1; shift
 for mode in buckets single vae; do
   SVDX_DIST_BACKEND=gloo SVDX_BENCH_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port $((29600 + RANDOM % 300)) bench.py --gpus 2 --steps 5 --warmup 2 --tiny --no-cpu-baseline --no-roofline --overlap $mode "$@" \
+    --master-port $((29600 + RANDOM % 300)) bench.py --full --gpus 2 --steps 5 --warmup 2 --tiny --no-cpu-baseline --no-roofline --overlap $mode "$@" \
     2> ${out}_${mode}.err | grep '^{' > ${out}_${mode}.json
   python - "$mode" "${out}_${mode}.json" <<'PY'
 import json, sys

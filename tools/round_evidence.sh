@@ -4,10 +4,10 @@
 # BASELINE.json on one GPU, the in-step A/B of the default-on paths, then the profiler passes of tools/collect_evidence.sh.
 # usage: gpurun --timeout 2400 -- 'bash tools/round_evidence.sh r4'
 tag=${1:-rX}; O=gpurun_out; mkdir -p $O
-python bench.py > $O/${tag}_bench_default_run.json 2> $O/${tag}_bench_default_run.err; tail -c 600 $O/${tag}_bench_default_run.json | head -c 300; echo
-python bench.py --dtype bf16 --no-cpu-baseline > $O/${tag}_bench_bf16.json 2>/dev/null
-python bench.py --lora-rank 64 --dtype bf16 --no-cpu-baseline > $O/${tag}_bench_c5.json 2>/dev/null
-python bench.py --frames 25 --height 576 --width 1024 --grad-accum 2 --steps 20 --no-cpu-baseline > $O/${tag}_bench_c4.json 2>/dev/null
+python bench.py --full > $O/${tag}_bench_default_run.json 2> $O/${tag}_bench_default_run.err; tail -c 600 $O/${tag}_bench_default_run.json | head -c 300; echo
+python bench.py --full --dtype bf16 --no-cpu-baseline > $O/${tag}_bench_bf16.json 2>/dev/null
+python bench.py --full --lora-rank 64 --dtype bf16 --no-cpu-baseline > $O/${tag}_bench_c5.json 2>/dev/null
+python bench.py --full --frames 25 --height 576 --width 1024 --grad-accum 2 --steps 20 --no-cpu-baseline > $O/${tag}_bench_c4.json 2>/dev/null
 for f in bf16 c5 c4; do python - <<PY
 import json
 d = json.loads(open("$O/${tag}_bench_$f.json").read().strip().splitlines()[-1]); c = d["config"]; r = d.get("roofline") or {}

@@ -57,6 +57,10 @@ def parse_args(argv=None):
     ap.add_argument("--adam_beta2", type=float, default=0.999)
     ap.add_argument("--adam_weight_decay", type=float, default=1e-2)
     ap.add_argument("--adam_epsilon", type=float, default=1e-8)
+    ap.add_argument("--max_grad_norm", type=float, default=1.0, help="max gradient norm (train_svd.py:468-470); used with --clip_grad_norm")
+    ap.add_argument("--clip_grad_norm", action="store_true",
+                    help="clip the gradient norm to --max_grad_norm: the accelerator.clip_grad_norm_ call train_svd.py:1045-1046 keeps "
+                         "commented out (without this switch the run is the reference's: no clipping)")
     ap.add_argument("--mixed_precision", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--checkpointing_steps", type=int, default=500)
     ap.add_argument("--checkpoints_total_limit", type=int, default=2)
@@ -182,7 +186,8 @@ def main(argv=None):
                                   "noise_aug_strength is batch-1 only, train_svd.py:955)")
     # trainable set (:758-766), AdamW (:767-773), mixed precision + DDP (:815): the Trainer
     trainer = Trainer(unet, dtype=dtype, lr=args.learning_rate, betas=(args.adam_beta1, args.adam_beta2),
-                      weight_decay=args.adam_weight_decay, eps=args.adam_epsilon, grad_accum=args.gradient_accumulation_steps)
+                      weight_decay=args.adam_weight_decay, eps=args.adam_epsilon, grad_accum=args.gradient_accumulation_steps,
+                      max_grad_norm=args.max_grad_norm if args.clip_grad_norm else None)                  # :1045-1046
     ema_unet = None
     if args.use_ema:                                                             # :677-679
         ema_unet = EMAModel(unet.parameters(), model_cls=UNetSpatioTemporalConditionModel, model_config=unet.config,
@@ -270,7 +275,8 @@ def main(argv=None):
         global_step += 1
         seen += 1
         if is_main:
-            print(f"step {global_step} train_loss {train_loss:.6f} lr {lr_scheduler.get_last_lr()[0]:.3e} "
+            gn = f" grad_norm {loop.last_grad_norm:.6f}" if loop.last_grad_norm is not None else ""
+            print(f"step {global_step} train_loss {train_loss:.6f}{gn} lr {lr_scheduler.get_last_lr()[0]:.3e} "
                   f"{(time.perf_counter() - t0) / seen * 1e3:.1f} ms/step", flush=True)
             if global_step % args.checkpointing_steps == 0:                      # :1059-1090
                 checkpoint.rotate_checkpoints(args.output_dir, args.checkpoints_total_limit)

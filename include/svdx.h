@@ -62,7 +62,7 @@ typedef struct svdx_gather {
 
 /* ABI revision of this header: bumped whenever an entry changes its argument list or meaning (100 = rounds 1-3; 400 = round 4).
  * svdx_version() returns the value the library was built with; the ctypes binding refuses a library whose number differs. */
-#define SVDX_VERSION 600
+#define SVDX_VERSION 610
 int         svdx_version(void);
 int         svdx_last_error(char* buf, size_t n);
 /* 1 when the binary was built for gfx950 and a device is usable */
@@ -385,7 +385,8 @@ int svdx_edm_loss(const void* pred, int ld, const float* noisy, const float* tar
 /* ---- optimizer: AdamW (train_svd.py:767-773) + GradScaler semantics (accelerate fp16) + the learning-rate schedule
  *      (diffusers get_scheduler, train_svd.py:807-813, stepped at :1048), all on device.
  *      opt_state float[SVDX_OPT_STATE_FLOATS]: 0 step (optimizer steps that were not skipped), 1 loss_scale, 2 growth_tracker,
- *      3 found_inf, 4 inv_scale, 5 bc1, 6 bc2, 7 skip, 8 lr multiplier of the current step (written by svdx_optim_prep),
+ *      3 found_inf, 4 inv_scale -- AdamW's gradient factor: 1 / the loss scale the backward pass used, times the clip coefficient when
+ *      svdx_grad_clip_coef ran after svdx_optim_prep --, 5 bc1, 6 bc2, 7 skip, 8 lr multiplier of the current step (written by svdx_optim_prep),
  *      9 schedule kind (SVDX_SCHED_*), 10 warmup steps, 11 total steps, 12 cycles, 13 power, 14 lr_end / lr_init (polynomial),
  *      15 scheduler steps per optimizer step (accelerate: num_processes; 0 is read as 1).
  *      Step k (1-based, skipped steps not counted) runs at lr * lambda((k - 1) * opt_state[15]). */
@@ -428,6 +429,29 @@ int svdx_adamw(float* p, const float* g, float* m, float* v, int64_t n, double l
 int svdx_adamw_tiled(float* p, const float* g, float* m, float* v, const int* tiles, int n_tiles, double lr, double beta1,
                      double beta2, double eps, double wd, double grad_mul, const float* opt_state, void* p_act, void* pt_act,
                      int param_mode, int dtype, void* stream);
+
+/* ---- gradient-norm clipping: accelerate's clip_grad_norm_(params, max_norm) (the call the reference's train_svd.py:1045-1046 keeps commented
+ *      out; --max_grad_norm, :468-470) on the flat gradient buffer, on device, without atomics or host synchronisation.  Two launches between
+ *      svdx_optim_prep and the AdamW entry of a step (on several ranks after the gradient sum, so every rank computes the same bits):
+ * svdx_grad_sumsq_spans: `spans` = n_spans triples (offset, count, tensor) of ints over g: offset a multiple of 4 (g 16-byte aligned),
+ *   0 <= count <= SVDX_CLIP_SPAN_FLOATS, any remainder mod 4.  partial (caller-owned scratch of n_spans doubles, 8-byte aligned):
+ *   partial[s] = the sum of the squares of span s, in fp64 (exact products; a fixed reduction order -- identical bits from run to run).
+ * svdx_grad_clip_coef: one workgroup.  The tensor column lists the tensors 0 .. n_tensors - 1 in order, each as a run of consecutive spans
+ *   (n_tensors <= SVDX_CLIP_MAX_TENSORS).  Sums every tensor's partials in span order and the tensors in a fixed order, then
+ *     total_norm = sqrt(sum) * opt_state[4] * grad_mul   (the unscaled gradient averaged over ranks and micro-batches: run it after
+ *                                                          svdx_optim_prep, which writes this step's opt_state[4])
+ *     coef       = min(1, max_norm / (total_norm + 1e-6))   (torch.nn.utils._clip_grads_with_norm_)
+ *   and writes out[0] = total_norm (before clipping: what accelerate returns), out[1] = coef (out: 2 floats).  Unless the step is skipped
+ *   (opt_state[7]) it folds the clip into AdamW's gradient factor: opt_state[4] *= coef (coef == 1 leaves it, and the step, bit-identical).
+ *   param_mode SVDX_PARAMS_BF16_REFERENCE follows torch on bf16 gradients: each per-tensor norm correctly rounded to bf16, the total rounded
+ *   to bf16, + 1e-6 / reciprocal / * max_norm each rounded to bf16, then the clamp; AdamW's rb16(g * opt_state[4] * grad_mul) is then
+ *   torch's rb16(g * coef) at one rank and one micro-batch.  Non-finite gradients give a non-finite total_norm; whether the step is taken
+ *   stays the inf check's decision.  Errors: thread-local, svdx_last_error(). */
+#define SVDX_CLIP_SPAN_FLOATS 65536
+#define SVDX_CLIP_MAX_TENSORS 8192
+int svdx_grad_sumsq_spans(const float* g, const int* spans, int n_spans, double* partial, void* stream);
+int svdx_grad_clip_coef(const double* partial, const int* spans, int n_spans, int n_tensors, double max_norm, double grad_mul,
+                        float* opt_state, float* out, int param_mode, void* stream);
 
 /* ---- EMA of the trainable weights (diffusers EMAModel.step, train_svd.py:1053-1054): shadow -= one_minus_decay * (shadow - p)
  *      over n floats (both buffers 16-byte aligned).  The decay itself follows EMAModel.get_decay on the host. */

@@ -202,6 +202,15 @@ __global__ __launch_bounds__(256) void ema_lerp_kernel(float* __restrict__ shado
 // bf16, on values held in the same float buffers (every stored value is bf16-representable).  Pinned to torch.optim.AdamW itself on
 // bf16 CPU tensors through the emulation (tests/test_host_logic.py).
 __device__ __forceinline__ float rb16(float x) { return (float)(bf16)x; }
+// x >= 0 correctly rounded to bf16 (ties to even) straight from fp64 -- no intermediate float rounding; beyond the bf16 range: inf
+__device__ __forceinline__ double rb16_f64(double x) {
+    if (!isfinite(x) || x == 0.0) return x;
+    int e = ilogb(x);
+    if (e < -126) e = -126;                                           // bf16 subnormals: fixed quantum 2^-133
+    const double q = ldexp(1.0, e - 7);
+    return (double)(float)(rint(x / q) * q);                          // 2^128 (a carry out of the top binade) becomes inf
+}
+
 struct AdamScalars {           // per-launch scalars of one AdamW step (device side)
     float gmul, decay, beta1, beta2, omb1, omb2, eps, step_size, bc2_sqrt, inv_bc2_sqrt;
 };
@@ -217,8 +226,13 @@ __device__ __forceinline__ AdamScalars adam_scalars(const float* st, double lr, 
     a.bc2_sqrt = sqrtf(st[6]);
     a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps;
     if (ref) {
-        a.decay = (float)(1.0 - lr * (double)st[8] * wd);
+        // torch forms the bias corrections, the step size and sqrt(bc2) in double from the step count as well
+        const double lr_d = lr * (double)st[8], step = (double)st[0];
+        a.step_size = (float)(lr_d / (1.0 - pow(beta1, step)));
+        a.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, step));
+        a.decay = (float)(1.0 - lr_d * wd);
         a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
+        a.eps = (float)rb16_f64(eps);                                 // add_(eps) on a bf16 tensor rounds the scalar to bf16 first
     } else {
         a.decay = 1.f - lr_f * (float)wd;
         a.omb1 = 1.f - a.beta1; a.omb2 = 1.f - a.beta2;
@@ -235,6 +249,8 @@ __device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v
         const float denom = sqrtf(v) * a.inv_bc2_sqrt + a.eps;
         p -= a.step_size * m / denom;
     } else {
+#pragma clang fp contract(off)
+        // every float op rounded on its own, as torch's CPU kernels do (the compiler's default would fuse addcmul_ and addcdiv_)
         const float gg = rb16(g * a.gmul);
         p = rb16(p * a.decay);
         m = rb16(fmaf(a.omb1, gg - m, m));                       // lerp_(grad, 1 - beta1): weight < 0.5, fused as torch's kernel
@@ -243,7 +259,7 @@ __device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v
         float d = rb16(sqrtf(v));
         d = rb16(d / a.bc2_sqrt);
         d = rb16(d + a.eps);
-        p = rb16(p + (-a.step_size) * (m / d));                  // addcdiv_(exp_avg, denom, value = -step_size)
+        p = rb16(p + (-a.step_size) * m / d);                    // addcdiv_(exp_avg, denom, value = -step_size): self + value * t1 / t2
     }
 }
 
@@ -345,6 +361,140 @@ __global__ __launch_bounds__(256) void adamw_tiled_kernel(float* __restrict__ p,
     }
 }
 
+// ---- gradient-norm clipping: accelerate's clip_grad_norm_ (the call the reference keeps commented out, train_svd.py:1045-1046) ----------
+// Squares are formed and summed in fp64: a product of two floats is exact there, no sum of squares of loss-scaled fp16 gradients can
+// overflow it, and the accumulated error stays far below one fp32 ulp of the norm.  Every sum has a fixed order and there are no atomics:
+// the same bits from run to run and on every rank.
+__device__ __forceinline__ double wave_sum_f64(double v) {           // xor butterfly: every lane ends with the same bits
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Pass 1: one workgroup per span (offset, count, tensor) of the table, count <= SVDX_CLIP_SPAN_FLOATS: partial[span] = sum of squares.
+// Lane order: four 16-byte loads in flight, squares accumulated with fp64 FMAs; then the wave butterfly and the four waves in order.
+__global__ __launch_bounds__(256) void grad_sumsq_spans_kernel(const float* __restrict__ g, const int* __restrict__ spans,
+                                                               double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int* sp = spans + (size_t)blockIdx.x * 3;
+    const float* src = g + (long)sp[0];
+    const int cnt = sp[1], n4 = cnt & ~3;
+    double acc = 0.0;
+    for (int i = threadIdx.x * 4; i < n4; i += 4 * 256 * 4) {
+        f32x4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = i + u * 256 * 4;
+            v[u] = j < n4 ? *reinterpret_cast<const f32x4*>(src + j) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = fma((double)v[u][e], (double)v[u][e], acc);
+    }
+    if ((int)threadIdx.x < cnt - n4) {                                // the 1..3 floats beyond the last whole vector
+        const double x = (double)src[n4 + threadIdx.x];
+        acc = fma(x, x, acc);
+    }
+    acc = wave_sum_f64(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Pass 2: one workgroup.  Tensor t's sum of squares: lane l adds the partials of its spans first_t + l, first_t + l + 64, ... in span order,
+// then the wave butterfly; wave w takes the tensors w, w + 16, ... in tensor order, the sixteen wave totals are added in wave order.
+//   total_norm = sqrt(sum) * opt_state[4] * grad_mul: the norm of the unscaled gradient averaged over ranks and micro-batches (what
+//   accelerate's clip_grad_norm_ sees), coef = min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils._clip_grads_with_norm_).
+// REF (SVDX_PARAMS_BF16_REFERENCE): torch's sequence on bf16 gradients -- every per-tensor norm rounded to bf16, their norm rounded to bf16,
+// then + 1e-6, the reciprocal and the product with max_norm (torch's `float / tensor`), each rounded to bf16, clamped to 1.
+// out = {total_norm, coef}; unless the step is skipped, opt_state[4] *= coef: AdamW's gradient factor applies the clip.
+// Both phases put CLIP_BATCH independent loads in flight before the first is used, and the butterflies of a batch are interleaved.  The
+// kernel is latency-bound: ~5 us per batch of 16 x CLIP_BATCH tensors on top of a 3.4 us launch (24 us for the 416 tensors / 6,334 spans
+// of the benched buffer, profiles/clip_grad_norm.md).
+constexpr int CLIP_WAVES = 16, CLIP_BATCH = 8;
+__global__ __launch_bounds__(CLIP_WAVES * 64) void grad_clip_coef_kernel(const double* __restrict__ partial, const int* __restrict__ spans,
+                                                                          int n_spans, int n_tensors, double max_norm, double grad_mul,
+                                                                          float* __restrict__ st, float* __restrict__ out, int ref) {
+    __shared__ int first[SVDX_CLIP_MAX_TENSORS + 1];
+    __shared__ double wtot[CLIP_WAVES];
+    for (int s0 = threadIdx.x; s0 < n_spans; s0 += CLIP_BATCH * CLIP_WAVES * 64) {      // where each tensor's run of spans begins
+        int tc[CLIP_BATCH], tp[CLIP_BATCH];
+#pragma unroll
+        for (int u = 0; u < CLIP_BATCH; ++u) {
+            const int s = s0 + u * CLIP_WAVES * 64;
+            tc[u] = s < n_spans ? spans[3 * s + 2] : -1;
+            tp[u] = s > 0 && s < n_spans ? spans[3 * s - 1] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < CLIP_BATCH; ++u) {
+            const int s = s0 + u * CLIP_WAVES * 64;
+            if (s < n_spans && tc[u] != tp[u] && tc[u] >= 0 && tc[u] < n_tensors) first[tc[u]] = s;
+        }
+    }
+    if (threadIdx.x == 0) first[n_tensors] = n_spans;
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double unscale = (double)st[4] * grad_mul;
+    double tot = 0.0;
+    for (int t0 = wave; t0 < n_tensors; t0 += CLIP_BATCH * CLIP_WAVES) {
+        // CLIP_BATCH tensors at once: round k adds every lane's span first_t + lane + 64 k of each of them (0.0 beyond the tensor's
+        // spans, which leaves a sum of squares unchanged) -- the per-tensor order of the additions, the loads of a round in flight together
+        double s[CLIP_BATCH];
+        int lo[CLIP_BATCH], hi[CLIP_BATCH], rounds = 0;
+#pragma unroll
+        for (int u = 0; u < CLIP_BATCH; ++u) {
+            const int t = t0 + u * CLIP_WAVES;
+            lo[u] = t < n_tensors ? max(first[t], 0) : 0;
+            hi[u] = t < n_tensors ? min(first[t + 1], n_spans) : 0;
+            rounds = max(rounds, (hi[u] - lo[u] + 63) / 64);          // wave-uniform
+            s[u] = 0.0;
+        }
+        for (int k = 0; k < rounds; ++k) {
+            double x[CLIP_BATCH];
+#pragma unroll
+            for (int u = 0; u < CLIP_BATCH; ++u) {
+                const int j = lo[u] + lane + 64 * k;
+                x[u] = j < hi[u] ? partial[j] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < CLIP_BATCH; ++u) s[u] += x[u];
+        }
+        // wave_sum_f64 of the CLIP_BATCH sums, interleaved: the same additions, the shuffle latencies overlap
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+            for (int u = 0; u < CLIP_BATCH; ++u) s[u] += __shfl_xor(s[u], o, 64);
+#pragma unroll
+        for (int u = 0; u < CLIP_BATCH; ++u) {
+            if (t0 + u * CLIP_WAVES >= n_tensors) break;
+            if (ref) {
+                const double nt = rb16_f64(sqrt(s[u]) * unscale);
+                tot += nt * nt;
+            } else {
+                tot += s[u];
+            }
+        }
+    }
+    if (lane == 0) wtot[wave] = tot;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double sum = 0.0;
+    for (int w = 0; w < CLIP_WAVES; ++w) sum += wtot[w];
+    float norm, coef;
+    if (ref) {
+        norm = (float)rb16_f64(sqrt(sum));
+        coef = rb16(rb16(1.f / rb16(norm + (float)rb16_f64(1e-6))) * (float)max_norm);     // (+ 1e-6: the scalar rounded to bf16, as add_ does)
+    } else {
+        norm = (float)(sqrt(sum) * unscale);
+        coef = (float)(max_norm / ((double)norm + 1e-6));
+    }
+    coef = coef > 1.f ? 1.f : coef;                                   // torch.clamp(max = 1): a NaN stays NaN
+    out[0] = norm;
+    out[1] = coef;
+    if (!(st[7] > 0.f)) st[4] *= coef;                                // a skipped step (st[7]) leaves AdamW's factor alone
+}
+
 }  // namespace
 
 extern "C" int svdx_edm_loss(const void* pred, int ld, const float* noisy, const float* target, const float* sigma,
@@ -409,6 +559,26 @@ extern "C" int svdx_optim_prep(float* opt_state, float beta1, float beta2, float
     hipLaunchKernelGGL(optim_prep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, opt_state, beta1, beta2, growth, backoff,
                        growth_interval, dynamic);
     SVDX_LAUNCH_CHECK("svdx_optim_prep");
+    return 0;
+}
+
+extern "C" int svdx_grad_sumsq_spans(const float* g, const int* spans, int n_spans, double* partial, void* stream) {
+    SVDX_CHECK_ARG(g && spans && partial && n_spans > 0 && ((uintptr_t)g & 15) == 0,
+                   "svdx_grad_sumsq_spans: bad args (non-null, n_spans > 0, g 16-byte aligned)");
+    hipLaunchKernelGGL(grad_sumsq_spans_kernel, dim3(n_spans), dim3(256), 0, (hipStream_t)stream, g, spans, partial);
+    SVDX_LAUNCH_CHECK("svdx_grad_sumsq_spans");
+    return 0;
+}
+
+extern "C" int svdx_grad_clip_coef(const double* partial, const int* spans, int n_spans, int n_tensors, double max_norm, double grad_mul,
+                                   float* opt_state, float* out, int param_mode, void* stream) {
+    SVDX_CHECK_ARG(partial && spans && opt_state && out && n_spans > 0 && n_tensors > 0 && n_tensors <= n_spans &&
+                       n_tensors <= SVDX_CLIP_MAX_TENSORS && max_norm > 0.0 && grad_mul > 0.0,
+                   "svdx_grad_clip_coef: bad args (1..%d tensors, each with >= 1 span; max_norm > 0)", SVDX_CLIP_MAX_TENSORS);
+    SVDX_CHECK_ARG(param_mode == SVDX_PARAMS_F32 || param_mode == SVDX_PARAMS_BF16_REFERENCE, "svdx_grad_clip_coef: param_mode %d", param_mode);
+    hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(CLIP_WAVES * 64), 0, (hipStream_t)stream, partial, spans, n_spans, n_tensors,
+                       max_norm, grad_mul, opt_state, out, param_mode);
+    SVDX_LAUNCH_CHECK("svdx_grad_clip_coef");
     return 0;
 }
 

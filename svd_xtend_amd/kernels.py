@@ -26,7 +26,7 @@ LN_PARTIAL_ROWS = 2048
 GN_REPLICAS = 8
 GN_STAT_FLOATS = 4             # floats of storage per (replica, sample, group) of a GroupNorm statistics buffer: two int64
 GATHER_PLAIN, GATHER_CONV3X3, GATHER_CONV3X3_DGRAD2, GATHER_TEMPORAL3, GATHER_CONV3X3_PAD0 = 0, 1, 2, 3, 4
-ABI_VERSION = 600              # include/svdx.h: SVDX_VERSION this binding was written against
+ABI_VERSION = 610              # include/svdx.h: SVDX_VERSION this binding was written against
 OPT_STATE_FLOATS = 16          # include/svdx.h: layout of the optimizer / loss-scale / schedule state
 SCHED_KINDS = {"constant": 0, "constant_with_warmup": 1, "linear": 2, "cosine": 3, "cosine_with_restarts": 4, "polynomial": 5, "piecewise_constant": 6}
 SCHED_MAX_RULES = 8            # include/svdx.h SVDX_SCHED_MAX_RULES: step rules of piecewise_constant, stored behind the 16 state floats
@@ -143,6 +143,8 @@ _SIGS = {
     "svdx_adamw": "pppp" "l" "dddddd" "pp" "iip",
     "svdx_adamw_tiled": "ppppp" "i" "dddddd" "ppp" "iip",
     "svdx_ema_lerp": "pp" "l" "f" "p",
+    "svdx_grad_sumsq_spans": "pp" "i" "pp",
+    "svdx_grad_clip_coef": "pp" "ii" "dd" "pp" "ip",
     "svdx_allreduce_grads": "p" "ii" "l" "i" "p",
     "svdx_plan_begin": "",
     "svdx_plan_end": "p",
@@ -156,6 +158,8 @@ EXPORTED_SYMBOLS = tuple(_SIGS) + ("svdx_wall_clock_khz", "svdx_version", "svdx_
 PARAMS_F32, PARAMS_BF16_REFERENCE = 0, 1      # include/svdx.h: param_mode of svdx_adamw / svdx_adamw_tiled
 TN_FLAT = 64                   # include/svdx.h SVDX_TN_FLAT: the staging of operands >= 2 GiB, on request (tests)
 MAX_PEERS = 16                 # include/svdx.h SVDX_MAX_PEERS: ranks of svdx_allreduce_grads
+CLIP_SPAN_FLOATS = 65536       # include/svdx.h SVDX_CLIP_SPAN_FLOATS: floats of one span of svdx_grad_sumsq_spans
+CLIP_MAX_TENSORS = 8192        # include/svdx.h SVDX_CLIP_MAX_TENSORS: tensors of one svdx_grad_clip_coef
 BATCH_MAX_JOBS = 48            # include/svdx.h SVDX_BATCH_MAX_JOBS: jobs of a *_batch entry that share one launch
 TSA_MAX_C, TSA_MAX_T, TSA_BAND_ROWS = 320, 16, 144
 
@@ -516,6 +520,20 @@ class HipBackend:
 
     def ema_lerp(self, shadow, p, n, one_minus_decay):
         self._call("svdx_ema_lerp", _f32(shadow), _f32(p), n, float(one_minus_decay), self._stream())
+
+    def grad_sumsq_spans(self, g, spans, n_spans, partial):
+        """include/svdx.h svdx_grad_sumsq_spans: spans int32 [n_spans, 3] (offset, count, tensor); partial float64 [>= n_spans]."""
+        assert spans.dtype == torch.int32 and spans.is_contiguous() and spans.numel() >= 3 * n_spans
+        assert partial.dtype == torch.float64 and partial.numel() >= n_spans
+        self._call("svdx_grad_sumsq_spans", _f32(g), spans.data_ptr(), n_spans, partial.data_ptr(), self._stream())
+
+    def grad_clip_coef(self, partial, spans, n_spans, n_tensors, max_norm, grad_mul, opt_state, out, param_mode=PARAMS_F32):
+        """include/svdx.h svdx_grad_clip_coef: out float32 [2] <- (total_norm, coef); opt_state[4] *= coef unless the step is skipped."""
+        assert partial.dtype == torch.float64 and partial.numel() >= n_spans and out.numel() >= 2
+        assert spans.dtype == torch.int32 and spans.is_contiguous() and spans.numel() >= 3 * n_spans
+        assert opt_state.numel() >= OPT_STATE_FLOATS
+        self._call("svdx_grad_clip_coef", partial.data_ptr(), spans.data_ptr(), n_spans, n_tensors, float(max_norm), float(grad_mul),
+                   _f32(opt_state), _f32(out), int(param_mode), self._stream())
 
     def allreduce_grads(self, peer_ptrs, rank, n, phase):
         """include/svdx.h svdx_allreduce_grads: peer_ptrs = device addresses of every rank's buffer (own included, index = rank)."""

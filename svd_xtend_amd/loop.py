@@ -65,7 +65,10 @@ class TrainLoop:
         self.graphed: Optional[GraphedStep] = None
         self.graph_conditioners = graph_conditioners and self.use_graph
         self.cond_graph = None
-        self._loss = torch.zeros(1, dtype=torch.float32, device=self.dev)
+        # the last step's loss and, with Trainer(max_grad_norm=...), its gradient norm: one device buffer, one host read per iteration
+        self._stats = torch.zeros(2, dtype=torch.float32, device=self.dev)
+        self._loss, self._grad_norm = self._stats[0:1], self._stats[1:2]
+        self.last_grad_norm: Optional[float] = None      # the norm before clipping (accelerate's return value); None without clipping
         self.global_step = 0
 
     # ---- conditioners + EDM data prep of one micro-batch, all on the device (train_svd.py:942-1017) ----------------------------
@@ -190,6 +193,8 @@ class TrainLoop:
 
     def _after_step(self) -> None:
         self._loss.copy_(self.tr.last_loss())            # the next zero_grad clears the loss slot: keep this step's value
+        if self.tr.clip_out is not None:
+            self._grad_norm.copy_(self.tr.clip_out[0:1])
         if self.ema is not None:
             self.ema.step(self.tr.model.parameters())
         self.global_step += 1
@@ -217,4 +222,7 @@ class TrainLoop:
             else:
                 self.tr.step(self.batches if self.tr.grad_accum > 1 else self.batches[0], side_work=side)
             self._after_step()
-        return float(self._loss)                         # the iteration's one host synchronisation (train_svd.py:1039-1041)
+        if self.tr.clip_out is None:
+            return float(self._loss)                     # the iteration's one host synchronisation (train_svd.py:1039-1041)
+        loss, self.last_grad_norm = self._stats.tolist()  # the same synchronisation, the gradient norm beside the loss
+        return loss

@@ -168,8 +168,12 @@ class Trainer:
     def __init__(self, model: UNetSpatioTemporalConditionModel, dtype: torch.dtype = torch.float16,
                  lr: float = 1e-5, betas=(0.9, 0.999), weight_decay: float = 1e-2, eps: float = 1e-8,
                  init_scale: float = 65536.0, growth_interval: int = 2000, process_group=None,
-                 grad_accum: int = 1, lora_param_dtype: Optional[str] = None):
-        """lora_param_dtype: None -- the trainable parameters and AdamW's moments are fp32 whatever the activation dtype (this library's
+                 grad_accum: int = 1, lora_param_dtype: Optional[str] = None, max_grad_norm: Optional[float] = None):
+        """max_grad_norm: None (the default: no clipping, the reference as it ships) or the `max_norm` of accelerate's
+        clip_grad_norm_(unet.parameters(), args.max_grad_norm) -- the call train_svd.py:1045-1046 keeps commented out.  Each optimizer step
+        then takes the L2 norm of the unscaled gradient averaged over ranks and micro-batches and scales it by min(1, max_norm / (norm + 1e-6))
+        on the device (svdx_grad_sumsq_spans + svdx_grad_clip_coef, include/svdx.h); `grad_norm` / `clip_coef` hold the last step's values.
+        lora_param_dtype: None -- the trainable parameters and AdamW's moments are fp32 whatever the activation dtype (this library's
         default; for LoRA under bf16 a measured improvement on the reference's recipe, profiles/r5_lora_dtype_deviation.json).
         "reference" -- the recipe of /root/reference/train_svd_lora.py:666-674 itself: with --mixed_precision bf16 the UNet is cast to bf16
         BEFORE add_adapter, so adapters, gradients and torch.optim.AdamW's state are bf16 tensors.  The parameters are rounded to bf16 once
@@ -180,6 +184,9 @@ class Trainer:
         if lora_param_dtype == "reference" and dtype != torch.bfloat16:
             raise ValueError("lora_param_dtype='reference' reproduces the bf16 recipe: pass dtype=torch.bfloat16")
         self.param_mode = K.PARAMS_BF16_REFERENCE if lora_param_dtype == "reference" else K.PARAMS_F32
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0 and float(max_grad_norm) < float("inf")):
+            raise ValueError(f"max_grad_norm={max_grad_norm!r}: None or a positive finite number")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.model, self.dtype = model, dtype
         self.lr, self.betas, self.wd, self.eps = lr, betas, weight_decay, eps
         self.growth_interval = growth_interval
@@ -205,6 +212,10 @@ class Trainer:
         st = [0.0] * K.OPT_STATE_ALLOC
         st[1], st[4], st[5], st[6], st[8] = (init_scale if self.dynamic else 1.0), 1.0, 1.0, 1.0, 1.0   # slots 9..15: schedule
         self.opt_state = torch.tensor(st, dtype=torch.float32, device=dev)
+        # gradient-norm clipping: (total_norm, coef) of the last optimizer step, written by svdx_grad_clip_coef
+        self.clip_out = torch.zeros(2, dtype=torch.float32, device=dev) if self.max_grad_norm is not None else None
+        self.grad_norm = self.clip_out[0] if self.clip_out is not None else None
+        self.clip_coef = self.clip_out[1] if self.clip_out is not None else None
         self.micro = 0
         self.schedule = dict(name="constant", num_warmup_steps=0, num_training_steps=0, num_cycles=0.0, power=1.0, lr_end=1e-7,
                              steps_per_step=1)
@@ -261,6 +272,20 @@ class Trainer:
         fin = [(c, min(n, self.n_flat - c)) for c, n in chunks if c < self.n_flat]
         self.finite_spans = torch.tensor(fin, dtype=torch.int32, device=dev).contiguous() if (self.rt.write_once and fin) else None
         self.rt.found_inf = self.opt_state[3:4] if (self.world == 1 and self.zero_spans is not None) else None
+        # gradient-norm clipping: every trainable tensor (parameter order) as spans of <= CLIP_SPAN_FLOATS floats of g_flat[0, n_flat) --
+        # not the alignment gaps, not the loss slot -- and one fp64 partial sum per span
+        self.clip_spans = self.clip_partial = None
+        self.n_clip_tensors = 0
+        if self.max_grad_norm is not None and self.params:
+            rows = []
+            for i, (p, off) in enumerate(zip(self.params, self.offsets)):
+                assert off % 4 == 0 and off + p.numel() <= self.n_flat
+                rows += [(off + c, min(K.CLIP_SPAN_FLOATS, p.numel() - c), i) for c in range(0, p.numel(), K.CLIP_SPAN_FLOATS)]
+            if len(self.params) > K.CLIP_MAX_TENSORS:
+                raise ValueError(f"gradient clipping: {len(self.params)} trainable tensors, the kernel takes {K.CLIP_MAX_TENSORS}")
+            self.clip_spans = torch.tensor(rows, dtype=torch.int32).contiguous().to(dev)
+            self.clip_partial = torch.zeros(len(rows), dtype=torch.float64, device=dev)
+            self.n_clip_tensors = len(self.params)
         # gradient buckets for overlapping the all-reduce with the backward sweep: one contiguous slice of g_flat per transformer
         # block (its trainables are adjacent in named_parameters order), reduced as soon as backward_rows leaves the block
         # default schedule of the gradient sum over ranks: ONE collective after the backward sweep (north_star's form).  True = one
@@ -490,6 +515,13 @@ class Trainer:
         self.rt.unchecked_grads = False
         k.optim_prep(self.opt_state, self.betas[0], self.betas[1], 2.0, 0.5, self.growth_interval, int(self.dynamic))
         grad_mul = 1.0 / (self.world * self.grad_accum)
+        if self.clip_spans is not None:
+            # clip_grad_norm_ on the summed buffer (after finish_grads: the same coefficient on every rank), folded into AdamW's gradient
+            # factor opt_state[4], which optim_prep has just written for this step
+            n_spans = self.clip_spans.shape[0]
+            k.grad_sumsq_spans(self.g_flat, self.clip_spans, n_spans, self.clip_partial)
+            k.grad_clip_coef(self.clip_partial, self.clip_spans, n_spans, self.n_clip_tensors, self.max_grad_norm, grad_mul,
+                             self.opt_state, self.clip_out, param_mode=self.param_mode)
         if self.adam_tiles is not None:
             k.adamw_tiled(self.p_flat, self.g_flat, self.m_flat, self.v_flat, self.adam_tiles, self.adam_tiles.shape[0], self.lr,
                           self.betas[0], self.betas[1], self.eps, self.wd, grad_mul, self.opt_state, self.rt.w16_flat,

@@ -225,17 +225,16 @@ __device__ __forceinline__ AdamScalars adam_scalars(const float* st, double lr, 
     a.inv_bc2_sqrt = rsqrtf(st[6]);
     a.bc2_sqrt = sqrtf(st[6]);
     a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps;
+    a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);     // as torch: formed in double (1.f - 0.999f moved every second moment by 1.3e-5 of its increment)
     if (ref) {
         // torch forms the bias corrections, the step size and sqrt(bc2) in double from the step count as well
         const double lr_d = lr * (double)st[8], step = (double)st[0];
         a.step_size = (float)(lr_d / (1.0 - pow(beta1, step)));
         a.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, step));
         a.decay = (float)(1.0 - lr_d * wd);
-        a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
         a.eps = (float)rb16_f64(eps);                                 // add_(eps) on a bf16 tensor rounds the scalar to bf16 first
     } else {
         a.decay = 1.f - lr_f * (float)wd;
-        a.omb1 = 1.f - a.beta1; a.omb2 = 1.f - a.beta2;
     }
     return a;
 }

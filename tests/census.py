@@ -3,7 +3,8 @@
 `census(name)` runs the second optimizer step of a configuration on a backend that performs no arithmetic and only records, per call,
 a hashable SIGNATURE of the launch (the host code never reads a value back from the device inside a step, so the whole step runs on
 it).  `run_case(backend, signature)` rebuilds seeded operands from the signature alone, launches the entry on the backend under test
-and judges every output against the float64 reference of tests/ref64.py with the error model below.
+and judges every output against the float64 reference of tests/ref64.py with the error model below.  `census_cond(name)` records the
+passes around the step the same way (COND_CONFIGS: VAE encode / decode, the CLIP image path, the sampler's batch-2 forward, packing, EMA).
 
 Signature = (entry, ((argument name, value), ...)) in the order of `kernels.HipBackend`'s method.  A value is an int / float / bool / None,
 a `kernels.Gather`, a tuple of per-job tuples for the `*_batch` entries, or -- for a tensor -- ("T", dtype name, alias, table, n) where
@@ -43,8 +44,9 @@ import emul  # noqa: E402  (the FORMAT of the fixed-point GroupNorm statistics b
 import ref64  # noqa: E402
 from kernel_checks import tol_for  # noqa: E402  (the project's bar for the multi-stage families)
 
-# entries that compute nothing numeric: memsets, the host-side state machine of the loss scale, the finite flag, launch plans, clocks
-ALLOW_LIST = ("zero", "zero_spans", "optim_prep", "check_finite", "check_finite_spans", "plan_begin", "plan_end", "stamp")
+# entries that compute nothing numeric: the host-side state machine of the loss scale, the finite flag, launch plans, clocks.  (The memsets
+# `zero` / `zero_spans` have runners: the bytes are zero and nothing beside them is touched.)
+ALLOW_LIST = ("optim_prep", "check_finite", "check_finite_spans", "plan_begin", "plan_end", "stamp")
 ALLOW_FRACTION = 0.02
 
 _PARAMS = {n: list(inspect.signature(f).parameters.values())[1:] for n, f in inspect.getmembers(K.HipBackend, inspect.isfunction)
@@ -109,6 +111,9 @@ def _enc(v, seen, name):
     raise TypeError(f"{name}: {type(v)}")
 
 
+_SIZED = {"zero": "t", "blur_axis": "taps"}        # entry -> the tensor argument whose element count the binding passes on (bytes / taps)
+
+
 def signature_of(entry, args, kwargs):
     params = _PARAMS[entry]
     vals = {p.name: p.default for p in params}
@@ -116,7 +121,10 @@ def signature_of(entry, args, kwargs):
         vals[p.name] = a
     vals.update(kwargs)
     seen = {}
-    return (entry, tuple((p.name, _enc(vals[p.name], seen, p.name)) for p in params))
+    kv = tuple((p.name, _enc(vals[p.name], seen, p.name)) for p in params)
+    if entry in _SIZED:
+        kv = tuple((k, v[:4] + (vals[k].numel(),)) if k == _SIZED[entry] else (k, v) for k, v in kv)
+    return (entry, kv)
 
 
 def sig_args(sig):
@@ -198,6 +206,153 @@ def census(name):
         tr.step(batches)
         rec.on = True
         tr.step(batches)
+    _CACHE[name] = rec.counts
+    return rec.counts
+
+
+# ---- the passes around the step ---------------------------------------------------------------------------------------------------------
+# name -> (pass, geometry, model configuration: "real" = the SVD checkpoint's, "small" = the small configurations of tests/test_vae.py /
+# tests/test_clip.py and the tiny UNet).  Recorded as the step is: host only, models built without weight initialisation, the recorder
+# switched on for the pass itself.  Activation type: float16, what `prepare()` defaults to and the validation path runs.
+VAE_SMALL = dict(in_channels=3, latent_channels=4, block_out_channels=(64, 128, 128, 128), layers_per_block=1, scaling_factor=0.18215)
+CLIP_SMALL = dict(hidden_size=320, intermediate_size=640, projection_dim=64, num_hidden_layers=2, num_attention_heads=4, image_size=56,
+                  patch_size=14, hidden_act="gelu")
+CLIP_LAYERS = 2                    # of ViT-H's 32: every layer launches the same signatures (census_cond asserts it on the real tower)
+COND_CONFIGS = {
+    # the real workload's geometries (host only: the dispatch classes the GPU geometries below must cover)
+    "encode_real": ("vae_encode", (14, 320, 512), "real"),
+    "decode_real": ("vae_decode", (1, 14, 40, 64), "real"),
+    "sampler_real": ("sampler_fwd", (2, 14, 40, 64), "real"),
+    "clip_real": ("clip_image", (1, 320, 512), "real"),
+    # what runs on the GPU
+    "encode_3x320x512": ("vae_encode", (3, 320, 512), "real"),
+    "encode_2x64x96": ("vae_encode", (2, 64, 96), "real"),
+    "encode_1x40x24": ("vae_encode", (1, 40, 24), "real"),          # 15 tokens: the padded reduction of the attention's second GEMM
+    "decode_1x4x40x64": ("vae_decode", (1, 4, 40, 64), "real"),
+    "decode_1x4x16x24": ("vae_decode", (1, 4, 16, 24), "real"),
+    "decode_2x2x5x3": ("vae_decode", (2, 2, 5, 3), "real"),
+    "sampler_2x14x40x64": ("sampler_fwd", (2, 14, 40, 64), "real"),
+    "sampler_2x3x16x24": ("sampler_fwd", (2, 3, 16, 24), "real"),
+    "clip_1x320x512": ("clip_image", (1, 320, 512), "real"),
+    "clip_small_ragged": ("clip_image", (2, 40, 72), "small"),        # tests/test_clip.py's small tower: 17 tokens, heads of 80
+    "clip_small_quick_gelu": ("clip_image", (1, 64, 56), "small_quick_gelu"),
+    "pack": ("pack", None, "real"),
+    "ema": ("ema", None, "real"),
+    # tiny: the emulation and the simulator on the CPU
+    "tiny_encode": ("vae_encode", (2, 16, 24), "small"),
+    "tiny_decode": ("vae_decode", (1, 2, 2, 3), "small"),
+    "tiny_clip": ("clip_image", (2, 40, 72), "small"),
+    "tiny_sampler": ("sampler_fwd", (2, 3, 16, 16), "small"),
+    "tiny_pack": ("pack", None, "small"),
+    "tiny_ema": ("ema", None, "small"),
+}
+COND_REAL = {"vae_encode": "encode_real", "vae_decode": "decode_real", "sampler_fwd": "sampler_real", "clip_image": "clip_real"}
+COND_GPU = {     # pass -> the configurations whose union runs on the GPU
+    "vae_encode": ("encode_3x320x512", "encode_2x64x96", "encode_1x40x24"),
+    "vae_decode": ("decode_1x4x40x64", "decode_1x4x16x24", "decode_2x2x5x3"),
+    "sampler_fwd": ("sampler_2x14x40x64", "sampler_2x3x16x24"),
+    "clip_image": ("clip_1x320x512", "clip_small_ragged", "clip_small_quick_gelu"),
+    "pack": ("pack",),
+    "ema": ("ema",),
+}
+COND_TINY = ("tiny_encode", "tiny_decode", "tiny_clip", "tiny_sampler", "tiny_pack", "tiny_ema")
+
+
+def _clip_config(kind):
+    if kind == "real":
+        return dict(num_hidden_layers=CLIP_LAYERS)
+    return dict(CLIP_SMALL, hidden_act="quick_gelu") if kind == "small_quick_gelu" else dict(CLIP_SMALL)
+
+
+def _finite(model):
+    """what `build()` / `prepare()` read on the host must be a number: the blend factors"""
+    for n, p in model.named_parameters():
+        if n.endswith("mix_factor"):
+            p.data.fill_(0.5)
+    return model
+
+
+def _cond_models(kind, which):
+    from oracle.unet import SVD_CONFIG, TINY_CONFIG, no_default_init
+    out = {}
+    with no_default_init():
+        if "vae" in which:
+            from svd_xtend_amd.vae import AutoencoderKLTemporalDecoder
+            out["vae"] = _finite(AutoencoderKLTemporalDecoder(**({} if kind == "real" else VAE_SMALL)))
+        if "clip" in which:
+            from svd_xtend_amd.clip import CLIPVisionModelWithProjection
+            out["clip"] = CLIPVisionModelWithProjection(**_clip_config(kind))
+        if "unet" in which:
+            from svd_xtend_amd.unet import UNetSpatioTemporalConditionModel
+            out["unet"] = _finite(UNetSpatioTemporalConditionModel(**dict(SVD_CONFIG if kind == "real" else TINY_CONFIG)))
+    return out
+
+
+def census_cond(name):
+    """Counter[signature] of one pass around the step (COND_CONFIGS).  Packing is behind the recorded launches except in `pack`, which
+    records `prepare()` of the three models and nothing else."""
+    if name in _CACHE:
+        return _CACHE[name]
+    what, geo, kind = COND_CONFIGS[name]
+    rec = Recorder()
+    rec.on = False
+    with _backend(rec), torch.no_grad():
+        if what == "vae_encode":
+            vae = _cond_models(kind, ("vae",))["vae"].prepare()
+            n, H, W = geo
+            rec.on = True
+            vae.encode(torch.empty(n, 3, H, W))
+        elif what == "vae_decode":
+            vae = _cond_models(kind, ("vae",))["vae"].prepare()
+            B, T, h, w = geo
+            rec.on = True
+            vae.decode(torch.empty(B * T, 4, h, w), num_frames=T)
+        elif what == "clip_image":
+            from svd_xtend_amd import clip as C
+            b, h, w = geo
+            tower = _cond_models(kind, ("clip",))["clip"].prepare()
+            rec.on = True
+            C.encode_image(torch.empty(b, 3, h, w), tower)
+            if name == "clip_real":              # the layers beyond the first CLIP_LAYERS add launches, not signatures
+                full = Recorder()
+                with _backend(full):
+                    from oracle.unet import no_default_init
+                    with no_default_init():
+                        whole = C.CLIPVisionModelWithProjection()
+                    whole.prepare()
+                    full.counts.clear()
+                    C.encode_image(torch.empty(b, 3, h, w), whole)
+                assert set(full.counts) == set(rec.counts), "the 32-layer tower launches signatures the 2-layer one does not"
+        elif what == "sampler_fwd":
+            unet = _cond_models(kind, ("unet",))["unet"]
+            for p in unet.parameters():
+                p.requires_grad_(False)
+            unet.prepare()
+            B, T, h, w = geo
+            cross = unet.config.cross_attention_dim
+            args = (torch.empty(B, T, 8, h, w), torch.tensor(1.0))
+            kw = dict(encoder_hidden_states=torch.empty(B, 1, cross), added_time_ids=torch.ones(B, 3), return_dict=False)
+            unet(*args, **kw)
+            rec.on = True
+            unet(*args, **kw)
+        elif what == "pack":
+            models = _cond_models(kind, ("vae", "clip", "unet"))
+            for p in models["unet"].parameters():
+                p.requires_grad_(False)
+            rec.on = True
+            for m in models.values():
+                m.prepare()
+        elif what == "ema":
+            from svd_xtend_amd.train import Trainer
+            from svd_xtend_amd.training_utils import EMAModel
+            unet = _cond_models(kind, ("unet",))["unet"]
+            Trainer(unet, dtype=torch.float16, lr=1e-5)           # configuration 2: the trainable set in the Trainer's flat master buffer
+            ema = EMAModel(unet.parameters())
+            ema.step(unet.parameters())
+            rec.on = True
+            ema.step(unet.parameters())
+        else:
+            raise KeyError(what)
     _CACHE[name] = rec.counts
     return rec.counts
 
@@ -523,8 +678,17 @@ def run_gemm(be, o, a):
         n_s, G = M // gn[1], N // gn[2]
         o.decl("gn.0", K.GN_REPLICAS * n_s * G * K.GN_STAT_FLOATS, lambda t: t.zero_(), out=True)
     o.alloc()
+    # a pitch wider than N (the VAE's score rows, conv_out's 8 columns in zeroed 64-wide rows): what lies between the rows is not the launch's
+    pitch = None
+    if mode != K.OUT_F32_SLAB and epi != K.EPI_GEGLU_BWD and a["ldc"] > N and M > 1:
+        pitch = torch.as_strided(o["C"], (M - 1, a["ldc"] - N), (a["ldc"], 1), o["C"].storage_offset() + N)
+        pitch_before = pitch.clone()
     _launch(be, o)
     res = []
+    if pitch is not None:
+        same = bool((pitch.view(torch.int16 if pitch.element_size() == 2 else torch.int32) ==
+                     pitch_before.view(torch.int16 if pitch.element_size() == 2 else torch.int32)).all())
+        res.append(("columns N..ldc of C untouched", 0.0 if same else float("inf"), ()))
     A = _v(o["A"], nsrc, g.cin, g.lda) if g is not None else _v(o["A"], M, Kd, a["lda"])
     B = _v(o["B"], N, Kd, a["ldb"])
     d2 = None
@@ -1001,11 +1165,11 @@ def _attn_chunks(nb, heads, S):
     return [(b, h0, min(heads, h0 + hs)) for b in range(nb) for h0 in range(0, heads, hs)]
 
 
-def _attn_derived_o(ref, Spv, smax, S, dt):
+def _attn_derived_o(ref, Spv, smax, S, dt, hd=64):
     """o = P V with P = exp(s - lse): P is rounded to the activation type before the matrix unit takes it (one rounding of every term of
     P|V|), the normaliser is a sum of the same P (another 2^-p of |o| <= P|V|), fp32 accumulation of S + 64 terms, an error of
     (64 + 2) 2^-23 max|q||k| scale in a score moves P by as much relatively (twice: numerator and normaliser), and the output is rounded."""
-    return (2 * _UA[dt] + (S + 64 + 2 * 66 * smax[..., None]) * 2.0 ** -23) * Spv + _half_ulp_after(ref, 2 * _UA[dt], dt)
+    return (2 * _UA[dt] + (S + hd + 2 * (hd + 2) * smax[..., None]) * 2.0 ** -23) * Spv + _half_ulp_after(ref, 2 * _UA[dt], dt)
 
 
 @runner("attn_fwd")
@@ -1524,6 +1688,318 @@ def run_grad_clip_coef(be, o, a):
     return res
 
 
+# ---- memsets -------------------------------------------------------------------------------------------------------------------------------
+def _all_bits_zero(t):
+    return bool((t.contiguous().view(torch.uint8) == 0).all())
+
+
+@runner("zero")
+def run_zero(be, o, a):
+    """every byte of the tensor is zero afterwards (a -0.0 is not); the guard bands either side are run_case's check"""
+    n = a["t"][4]
+    o.decl("t", n, lambda t: t.fill_(1.0), out=True)
+    o.alloc()
+    _launch(be, o)
+    return [("all bytes zero", 0.0 if _all_bits_zero(o["t"]) else float("inf"), ())]
+
+
+@runner("zero_spans")
+def run_zero_spans(be, o, a):
+    """include/svdx.h: spans int32 [n_spans, 2] (offset, count in floats, count a multiple of 4): those floats are zero bytes afterwards,
+    every other float of the buffer keeps its value"""
+    spans = o.table("spans").view(-1, 2)[:a["n_spans"]]
+    n = int((spans[:, 0] + spans[:, 1]).max())
+    o.decl("base", n, lambda t: t.fill_(1.0), out=True)
+    o.alloc()
+    _launch(be, o, dict(spans=o["spans"].view(-1, 2)))
+    inside = torch.zeros(n + 1, dtype=torch.int32, device=o.dev)
+    inside.index_add_(0, spans[:, 0].to(o.dev), torch.ones(len(spans), dtype=torch.int32, device=o.dev))
+    inside.index_add_(0, (spans[:, 0] + spans[:, 1]).to(o.dev), -torch.ones(len(spans), dtype=torch.int32, device=o.dev))
+    inside = inside.cumsum(0)[:n] > 0
+    bits = o["base"].view(torch.int32)
+    return [("spans: all bytes zero", 0.0 if bool((bits[inside] == 0).all()) else float("inf"), ()),
+            ("outside the spans untouched", 0.0 if bool((o["base"][~inside] == 1.0).all()) else float("inf"), ())]
+
+
+# ---- the conditioners' own kernels (csrc/encoders.hip) and the layout passes --------------------------------------------------------------
+@runner("patch_rows")
+def run_patch_rows(be, o, a):
+    """out = round(mul * in) at the im2col position: one product in fp32 (none when mul == 1: K_acc = 0, E = 1 / 0), one rounding.
+    include/svdx.h: the columns C*kh*kw .. ldk are ZERO (the GEMM behind it reduces over them)."""
+    n, C, H, W, kh, kw, ho, wo, ldk = (a[k] for k in ("n_img", "C", "H", "W", "kh", "kw", "ho", "wo", "ldk"))
+    o.mat("inp", 1, n * C * H * W, scale=0.5)
+    o.out("out", n * ho * wo, ldk)
+    o.alloc()
+    _launch(be, o)
+    ref = ref64.patch_rows(o["inp"].view(n, C, H, W), kh, kw, a["stride"], a["pad"], ldk, a["mul"])
+    got = _v(o["out"], n * ho * wo, ldk, ldk)
+    res = []
+    judge_single(res, "out", got, ref, ref.abs(), 0, 0 if a["mul"] == 1.0 else 1)
+    kk = C * kh * kw
+    if ldk > kk:
+        judge_exact(res, "padding columns are zero", got[:, kk:], torch.zeros_like(got[:, kk:]))
+    return res
+
+
+@runner("transpose")
+def run_transpose(be, o, a):
+    rows, cols, ld_in, ld_out = a["rows"], a["cols"], a["ld_in"], a["ld_out"]
+    o.mat("inp", rows, cols, ld_in)
+    o.out("out", cols, ld_out)
+    o.alloc()
+    _launch(be, o)
+    ref = torch.zeros(cols, ld_out, dtype=o.dtype("inp"), device=o.dev)
+    ref[:, :rows] = _v(o["inp"], rows, cols, ld_in).t()
+    res = []
+    judge_exact(res, "out (a move: bit-exact, the columns rows..ld_out zero)", _v(o["out"], cols, ld_out, ld_out), ref)
+    return res
+
+
+@runner("rows_to_nchw")
+def run_rows_to_nchw(be, o, a):
+    n, C, H, W, ld = a["n_img"], a["C"], a["H"], a["W"], a["ld"]
+    o.mat("inp", n * H * W, C, ld)
+    o.out("out", 1, n * C * H * W)
+    o.alloc()
+    _launch(be, o)
+    ref = _v(o["inp"], n * H * W, C, ld).to(torch.float64).view(n, H * W, C).permute(0, 2, 1).reshape(-1)
+    res = []
+    judge_exact(res, "out (a widening move: exact)", o["out"], ref)
+    return res
+
+
+@runner("cast_from_f32")
+def run_cast_from_f32(be, o, a):
+    n = a["n"]
+    o.mat("inp", 1, n, scale=0.05)
+    o.out("out", 1, n)
+    o.alloc()
+    _launch(be, o)
+    x = ref64.d(o["inp"])
+    res = []
+    judge_single(res, "out", o["out"], x, x.abs(), 0, 0)             # one rounding, nothing else
+    return res
+
+
+@runner("cast_transpose_from_f32")
+def run_cast_transpose_from_f32(be, o, a):
+    R, Cc = a["R"], a["Ccols"]
+    o.mat("inp", R, Cc, scale=0.05)
+    o.out("out", Cc, R)
+    o.alloc()
+    _launch(be, o)
+    x = ref64.d(_v(o["inp"], R, Cc, Cc)).t()
+    res = []
+    judge_single(res, "out", _v(o["out"], Cc, R, R), x, x.abs(), 0, 0)
+    return res
+
+
+@runner("ema_lerp")
+def run_ema_lerp(be, o, a):
+    """shadow -= omd (shadow - p) in fp32, omd as the float the binding passes: the difference, the product, the subtraction -- three
+    roundings (E = 3) of values bounded by S = |shadow| + omd (|shadow| + |p|)"""
+    n = a["n"]
+    o.decl("shadow", n, lambda t: t.copy_(o.randn(n, scale=0.05)), out=True)
+    o.mat("p", 1, n, scale=0.05)
+    o.alloc()
+    s0 = o["shadow"].clone()
+    _launch(be, o)
+    omd = float(torch.tensor(a["one_minus_decay"], dtype=torch.float32))
+    res, CH = [], 1 << 26
+    worst = (0.0, ())
+    for i0 in range(0, n, CH):
+        s, w = ref64.d(s0[i0:i0 + CH]), ref64.d(o["p"][i0:i0 + CH])
+        ref, S = ref64.ema_lerp(s, w, omd)
+        wv = _worst(_ratio(o["shadow"][i0:i0 + CH], ref, 0.5 * ulp_of(ref, torch.float32) + 3 * 2.0 ** -23 * S))
+        worst = max(worst, (wv[0], tuple(i0 + i for i in wv[1])))
+    return [("shadow",) + worst]
+
+
+# -- activations.  csrc/common.h computes no libm function: the normal CDF comes from Abramowitz & Stegun 7.1.26 (published bound of the
+# approximation in exact arithmetic: |erf error| <= 1.5e-7, i.e. 0.75e-7 on the CDF) evaluated with one v_exp_f32, one v_rcp_f32 and fp32
+# FMAs; the sigmoid is v_rcp_f32(1 + v_exp_f32(.)).  The CDNA ISA guide gives both transcendental instructions 1 ulp, and both flush fp32
+# denormals: a result below 2^-126 is zero.  Everything else is counted roundings (units of 2^-23 = one fp32 spacing of a value in [1, 2)).
+AS_ERF_BOUND = 1.5e-7
+_AS_P, _AS_A = 0.3275911, (0.254829592, -0.284496736, 1.421413741, -1.453152027, 1.061405429)
+FP32_MIN_NORMAL = 2.0 ** -126
+
+
+def gelu_cdf_error(x):
+    """absolute error bound of gelu_parts(x).cdf for float64 x (any shape): h = P(t) E with t = 1 / (1 + p |x| / sqrt 2), E = exp(-x^2 / 2),
+    P the degree-5 polynomial without constant term.  Relative error of h, in units of 2^-23:
+      E: the two products of its argument a = x^2 log2(e) / 2 move it by 2^-23 a absolutely, E by ln 2 of that relatively: 0.7 a; v_exp: 1
+      t: one FMA (1/2), v_rcp (1): 1.5, carried to P by its relative sensitivity kappa = |t P'(t) / P(t)|
+      P: four FMAs and two products, each a rounding of a partial sum bounded by sum |a_i| t^i: 3 cond, cond = that sum / |P(t)|
+    then 1 - h for x >= 0 (1/2), the published bound of the approximation itself, and the flush of h below the smallest normal."""
+    ax = x.abs()
+    t = 1.0 / (1.0 + _AS_P * ax / math.sqrt(2.0))
+    pw = torch.stack([t ** (i + 1) for i in range(5)])
+    co = torch.tensor(_AS_A, dtype=torch.float64, device=x.device).view(5, *([1] * x.ndim))
+    P = (co * pw).sum(0)
+    dP = (co * pw * torch.arange(1, 6, dtype=torch.float64, device=x.device).view(5, *([1] * x.ndim))).sum(0)        # t P'(t)
+    cond = (co.abs() * pw).sum(0) / P.abs()
+    kappa = dP.abs() / P.abs()
+    h = 0.5 * P * torch.exp(-0.5 * x * x)
+    units = 0.7 * (0.5 * x * x * math.log2(math.e)) + 1.0 + 1.5 * kappa + 3.0 * cond
+    return h * units * 2.0 ** -23 + 2.0 ** -24 + 0.5 * AS_ERF_BOUND + FP32_MIN_NORMAL
+
+
+def act_bound(x, act, dt, ref):
+    """per-element bound of act_rows / the GEGLU gate for float64 inputs x: half an output spacing + |x| (error of the CDF / sigmoid) + the
+    rounding of the product"""
+    if act == 0:
+        inner = gelu_cdf_error(x)
+    else:
+        # y = 1.702 x, the argument -log2(e) y (two roundings of |arg|: e moves by 0.7 |arg| units relatively), v_exp (1), 1 + e (1/2),
+        # v_rcp (1): s = 1 / (1 + e) moves by (1 - s) times e's error plus 1.5; a flushed result costs the smallest normal
+        arg = (1.702 * math.log2(math.e)) * x.abs()
+        s = torch.sigmoid(1.702 * x)
+        inner = s * ((1.0 - s) * (0.7 * arg + 1.0) + 1.5) * 2.0 ** -23 + FP32_MIN_NORMAL
+    return 0.5 * ulp_of(ref, dt) + x.abs() * inner + 2.0 ** -24 * ref.abs()
+
+
+def judge_act(res, label, got, x, act, gate=None):
+    """out = [gate *] act(x): class by class.  Finite inputs: the derived bound (a finite reference wants a finite result); NaN and
+    infinite inputs: the reference's class -- NaN, or the infinity / zero with its sign."""
+    x64 = ref64.d(x)
+    ref = ref64.act(x64, act)
+    g64 = None if gate is None else ref64.d(gate)
+    bound = act_bound(torch.where(torch.isfinite(x64), x64, torch.zeros_like(x64)), act, got.dtype, ref)
+    if g64 is not None:
+        # a * gelu(g): gelu(g) stays in fp32, one more product rounding
+        bound = g64.abs() * (bound - 0.5 * ulp_of(ref, got.dtype)) + 0.5 * ulp_of(g64 * ref, got.dtype) + 2.0 ** -24 * (g64 * ref).abs()
+        ref = g64 * ref
+    fin = torch.isfinite(x64) & torch.isfinite(ref)
+    g = got.to(torch.float64)
+    res.append((label,) + _worst(torch.where(fin, _ratio(got, torch.where(fin, ref, torch.zeros_like(ref)), bound), torch.zeros_like(ref))))
+    same = torch.where(torch.isnan(ref), torch.isnan(g), (g == ref) & (torch.signbit(g) == torch.signbit(ref)))
+    wrong = ~fin & ~same
+    res.append((label + ": class of the result at NaN / infinite inputs", float("inf") if bool(wrong.any()) else 0.0,
+                tuple(int(i) for i in wrong.nonzero()[0]) if bool(wrong.any()) else ()))
+    if got.dtype in (torch.float16, torch.bfloat16) and bool(fin.all()):
+        RoundingMeans().add(got, ref, got.dtype).report(res, label)
+
+
+@runner("act_rows")
+def run_act_rows(be, o, a):
+    n = a["n"]
+    o.mat("inp", 1, n, scale=2.0)
+    o.out("out", 1, n)                 # the CLIP tower runs it in place: `out` then aliases `inp` and the pre-fill is overwritten by the input
+    o.alloc()
+    x = o["inp"].clone()
+    _launch(be, o)
+    res = []
+    judge_act(res, "out", o["out"], x, a["act"])
+    return res
+
+
+@runner("geglu_fwd")
+def run_geglu_fwd(be, o, a):
+    M, Fd = a["M"], a["F"]
+    o.mat("pre", M, 2 * Fd)
+    o.out("out", M, Fd)
+    o.alloc()
+    _launch(be, o)
+    pre = _v(o["pre"], M, 2 * Fd, 2 * Fd)
+    res = []
+    judge_act(res, "out", _v(o["out"], M, Fd, Fd), pre[:, Fd:], 0, gate=pre[:, :Fd])
+    return res
+
+
+@runner("softmax_rows")
+def run_softmax_rows(be, o, a):
+    """p = exp2(x sl2 - max sl2) / sum, sl2 = scale log2(e) as a float.  Rounding points: the input (given) and the output; fp32 between.
+    The argument of the exponential is an FMA against the rounded maximum: with the rounding of sl2 itself, 2^-23 (|x| + |max|) sl2
+    absolutely (log2 units), ln 2 of that relatively on p -- twice, numerator and normaliser; v_exp 1 ulp, twice; the sum of `cols`
+    positive terms, the reciprocal, the product: (cols + 3) / 2 ... counted whole below.  Ceiling: the family's bar, tol_for(dt), on the row's
+    own maximum.  Columns cols..cols_out are ZERO (include/svdx.h): the P v GEMM behind it reduces over them."""
+    rows, cols, cols_out, ld_in, ld_out, sc = (a[k] for k in ("rows", "cols", "cols_out", "ld_in", "ld_out", "scale"))
+    o.mat("inp", rows, cols, ld_in, scale=3.0)
+    o.out("out", rows, cols_out, ld_out)
+    o.alloc()
+    x = ref64.d(_v(o["inp"], rows, cols, ld_in)).clone()
+    _launch(be, o)
+    dt = o.dtype("inp")
+    sl2 = float(torch.tensor(sc, dtype=torch.float32)) * math.log2(math.e)
+    ref = torch.softmax(x * float(torch.tensor(sc, dtype=torch.float32)), -1)
+    amag = (x.abs() + x.abs().amax(-1, keepdim=True)) * abs(sl2)
+    derived = ref * (2 * 0.7 * amag + 2 + cols + 3) * 2.0 ** -23 + 0.5 * ulp_of(ref, dt)
+    got = _v(o["out"], rows, cols_out, ld_out)
+    res = []
+    judge_rows(res, "out", got[:, :cols], ref, tol_for(dt), derived)
+    if cols_out > cols:
+        judge_exact(res, "padding columns are zero", got[:, cols:], torch.zeros_like(got[:, cols:]))
+    return res
+
+
+@runner("attn_small_fwd")
+def run_attn_small_fwd(be, o, a):
+    """csrc/attention.hip's arithmetic at a head dimension d <= dp <= 128: the bound of attn_fwd with d in place of 64 and the bar
+    tests/kernel_checks.py holds this family to, tol_for(dt), on the row's own maximum (a row holds all heads).  The padding channels
+    d..dp of every head are written as zeros."""
+    n, S, heads, d, dp, ld, ld_o, sc = (a[k] for k in ("n_img", "S", "heads", "d", "dp", "ld", "ld_o", "scale"))
+    o.mat("qkv", n * S, 3 * heads * dp, ld)
+    o.out("out", n * S, heads * dp, ld_o)
+    o.alloc()
+    _launch(be, o)
+    dt = o.dtype("qkv")
+    x = torch.as_strided(o["qkv"], (n, 3, heads, S, dp), (S * ld, heads * dp, dp, ld, 1), o["qkv"].storage_offset())
+    got = torch.as_strided(o["out"], (n, heads, S, dp), (S * ld_o, dp, ld_o, 1), o["out"].storage_offset())
+    ref, _, Spv, smax = ref64.attention(x[:, 0, ..., :d], x[:, 1, ..., :d], x[:, 2, ..., :d], sc)
+    bar = tol_for(dt) * ref.abs().amax((1, 3), keepdim=True).expand_as(ref)
+    bound = torch.maximum(torch.minimum(bar, _attn_derived_o(ref, Spv, smax, S, dt, d)), 0.5 * ulp_of(ref, dt))
+    res = [("out",) + _worst(_ratio(got[..., :d], ref, bound))]
+    RoundingMeans().add(got[..., :d], ref, dt).report(res, "out")
+    if dp > d:
+        judge_exact(res, "padding channels are zero", got[..., d:], torch.zeros_like(got[..., d:]))
+    return res
+
+
+def gaussian_taps(nt, dev):
+    """normalised Gaussian window of nt taps, sigma = nt / 4 (clip._gaussian_taps: the window is about 4 sigma)"""
+    xs = torch.arange(nt, dtype=torch.float32) - nt // 2
+    g = torch.exp(-xs.pow(2) / (2 * (nt / 4.0) ** 2))
+    return (g / g.sum()).to(dev)
+
+
+@runner("blur_axis")
+def run_blur_axis(be, o, a):
+    """out = sum_k taps[k] in[reflect(i + k - half)] in fp32: nt products (E = nt, unless contracted) and nt accumulations (K_acc = nt)"""
+    planes, H, W, axis, nt = a["planes"], a["H"], a["W"], a["axis"], a["taps"][4]
+    o.mat("inp", 1, planes * H * W, scale=0.5)
+    o.decl("taps", nt, lambda t: t.copy_(gaussian_taps(nt, o.dev)))
+    o.out("out", 1, planes * H * W)
+    o.alloc()
+    _launch(be, o)
+    ref, S = ref64.blur_axis(o["inp"].view(planes, H, W), o["taps"], axis)
+    res = []
+    judge_single(res, "out", o["out"].view(planes, H, W), ref, S, nt, nt)
+    return res
+
+
+@runner("bicubic_affine")
+def run_bicubic_affine(be, o, a):
+    """out = scale[c] bicubic(in)(y ry, x rx) + shift[c], align_corners, A = -0.75, all fp32.  Counted: 16 + 4 products and as many
+    accumulations (K_acc = 20, E = 20), the two affine operations (E + 2), against S = |scale| sum |wy| |wx| |in| + |shift|.  On top, from
+    the coordinate arithmetic: the source coordinate ry * yo carries two roundings (the ratio, the product), 2^-23 of its magnitude,
+    which moves every weight by its derivative (`pos`); and each weight is a cubic in Horner form whose partial sums reach 36 (outer
+    taps: |A| x^3 + 5 |A| x^2 + 8 |A| x + 4 |A| at x = 2) and 4.5 (inner taps), one rounding each: `wgt`."""
+    n, C, H, W, ho, wo = (a[k] for k in ("n_img", "C", "H", "W", "ho", "wo"))
+    o.mat("inp", 1, n * C * H * W, scale=0.5)
+    o.vec("scale", C, scale=0.2, shift=2.0)
+    o.vec("shift", C, scale=0.5)
+    o.out("out", 1, n * C * ho * wo)
+    o.alloc()
+    _launch(be, o)
+    x = o["inp"].view(n, C, H, W)
+    ref = ref64.bicubic_affine(x, ho, wo, o["scale"], o["shift"])
+    S, pos, wgt = ref64.bicubic_magnitudes(x, ho, wo)
+    sc, sh = ref64.d(o["scale"]).abs().view(1, C, 1, 1), ref64.d(o["shift"]).abs().view(1, C, 1, 1)
+    res = []
+    judge_single(res, "out", o["out"].view(n, C, ho, wo), ref, sc * S + sh, 20, 22, extra=2.0 ** -23 * sc * (pos + wgt))
+    return res
+
+
 # ---- what the tests iterate over ---------------------------------------------------------------------------------------------------------
 _FLAG_ARGS = ("out_mode", "epilogue", "trans", "silu_in", "accumulate", "silu", "prezeroed", "defer_reduce", "accumulate_f32", "variant", "mod",
               "rv_mod", "param_mode", "stages")
@@ -1547,6 +2023,56 @@ def feature_key(sig):
         elif k in ("split_k", "nsplit"):
             key.append((k, v > 1))
     return tuple(key)
+
+
+def dispatch_class(sig):
+    """What decides which code a launch runs, without its extents: the entry, the dtypes of its tensors, every flag argument; for `gemm`
+    also the tile it resolves to, whether K is split, the gather's kind, fused GroupNorm statistics, which epilogue operands are there,
+    and N and K (the weight's shape: the tile rules and the K loop depend on them; M is what the geometry scales)."""
+    entry, kv = sig
+    a = dict(kv)
+    key = [entry]
+    for k, v in kv:
+        if isinstance(v, tuple) and v and v[0] == "T":
+            key.append((k, v[1]))
+        elif k in _FLAG_ARGS and not (entry == "gemm" and k == "variant"):
+            key.append((k, bool(v) if k in ("mod", "rv_mod") else v))
+    if entry == "gemm":
+        from svd_xtend_amd.ops import _tile_launched
+        g = a["gather"]
+        key += [("tile", _tile_launched(a["variant"], a["M"], a["N"])), ("split", a["split_k"] > 1),
+                ("gather", None if g is None else (g.mode, g.stride, g.ups)), ("gn", a["gn"] is not None),
+                ("operands", tuple(a[k] is not None for k in ("bias", "rowvec", "res", "dual", "aux_out", "aux_in"))), ("N", a["N"]), ("K", a["K"])]
+    return tuple(key)
+
+
+def cond_gpu_signatures(what):
+    """{part name: Counter[signature]} of what the GPU test runs for pass `what`: the small geometries of COND_GPU and, under the name of
+    the real geometry, those of ITS signatures whose dispatch class none of the small geometries reaches (tiles chosen from the row count)."""
+    parts = collections.OrderedDict((n, census_cond(n)) for n in COND_GPU[what])
+    if what in COND_REAL:
+        reached = {dispatch_class(s) for c in parts.values() for s in c}
+        real = census_cond(COND_REAL[what])
+        rest = collections.Counter({s: n for s, n in real.items() if dispatch_class(s) not in reached})
+        if rest:
+            parts[COND_REAL[what]] = rest
+    return parts
+
+
+def run_act_exhaustive(be, dt, act, dev):
+    """every bit pattern of the 16-bit type `dt` through svdx_act_rows in ONE launch: [(label, excess, index = the bit pattern)]"""
+    be = getattr(be, "impl", be)
+    x = torch.arange(65536, dtype=torch.int32, device=dev).to(torch.int16).view(dt)
+    buf = torch.full((65536 + 2 * GUARD,), GUARD_VALUE, dtype=dt, device=dev)
+    out = buf[GUARD:GUARD + 65536]
+    out.fill_(1.0)
+    be.act_rows(x, out, 65536, act)
+    _sync(dev)
+    res = []
+    judge_act(res, "out", out, x, act)
+    ok = bool((buf[:GUARD] == GUARD_VALUE).all()) and bool((buf[-GUARD:] == GUARD_VALUE).all())
+    res.append(("nothing written outside the operands", 0.0 if ok else float("inf"), ()))
+    return res
 
 
 def coverage(counts):

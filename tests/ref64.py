@@ -264,3 +264,79 @@ def timestep_embed(t, dim):
     f = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float64, device=t.device) / half)
     arg = d(t)[:, None] * f[None]
     return torch.cat([torch.cos(arg), torch.sin(arg)], 1), torch.cat([arg, arg], 1).abs()
+
+
+# ---- the conditioners' kernels ----------------------------------------------------------------------------------------------------------
+def patch_rows(x, kh, kw, stride, pad, ldk, mul):
+    """im2col rows [n*ho*wo, ldk] of x [n, C, H, W]: F.unfold's order k = (c*kh + dy)*kw + dx, zero padding, times `mul` as the float the
+    binding passes; the columns C*kh*kw .. ldk are zero."""
+    n, C = x.shape[:2]
+    m = float(torch.tensor(mul, dtype=torch.float32))
+    cols = F.unfold(d(x) * m, (kh, kw), padding=pad, stride=stride)                    # [n, C*kh*kw, ho*wo]
+    out = torch.zeros(n * cols.shape[2], ldk, dtype=torch.float64, device=x.device)
+    out[:, :C * kh * kw] = cols.permute(0, 2, 1).reshape(-1, C * kh * kw)
+    return out
+
+
+def act(x, kind):
+    """0: exact-erf GELU, 1: x sigmoid(1.702 x) (CLIP's quick_gelu)"""
+    x = d(x)
+    return F.gelu(x) if kind == 0 else x * torch.sigmoid(1.702 * x)
+
+
+def ema_lerp(s, p, omd):
+    """(shadow - omd (shadow - p), its magnitude sum)"""
+    s, p = d(s), d(p)
+    return s - omd * (s - p), s.abs() + abs(omd) * (s.abs() + p.abs())
+
+
+def blur_axis(x, taps, axis):
+    """x [planes, H, W]; odd tap count, reflect padding; axis 0 = along W, 1 = along H: (value, magnitude sum)"""
+    half = (taps.numel() - 1) // 2
+    x4, t = d(x)[:, None], d(taps)
+    if axis == 0:
+        f = lambda v, w: F.conv2d(F.pad(v, (half, half, 0, 0), mode="reflect"), w.view(1, 1, 1, -1))
+    else:
+        f = lambda v, w: F.conv2d(F.pad(v, (0, 0, half, half), mode="reflect"), w.view(1, 1, -1, 1))
+    return f(x4, t)[:, 0], f(x4.abs(), t.abs())[:, 0]
+
+
+def bicubic_affine(x, ho, wo, scale, shift):
+    """torch's bicubic (A = -0.75) with align_corners=True, then the per-channel affine; x [n, C, H, W]"""
+    C = x.shape[1]
+    return F.interpolate(d(x), size=(ho, wo), mode="bicubic", align_corners=True) * d(scale).view(1, C, 1, 1) + d(shift).view(1, C, 1, 1)
+
+
+def _cubic(t, A=-0.75):
+    """(|weights|, |d weight / dt|) of the four taps at fraction t, [len, 4]"""
+    x0, x1, x2, x3 = t + 1, t, 1 - t, 2 - t
+    outer = lambda x: ((A * x - 5 * A) * x + 8 * A) * x - 4 * A
+    inner = lambda x: ((A + 2) * x - (A + 3)) * x * x + 1
+    douter = lambda x: (3 * A * x - 10 * A) * x + 8 * A
+    dinner = lambda x: (3 * (A + 2) * x - 2 * (A + 3)) * x
+    w = torch.stack([outer(x0), inner(x1), inner(x2), outer(x3)], 1)
+    dw = torch.stack([douter(x0), dinner(x1), dinner(x2), douter(x3)], 1)
+    return w.abs(), dw.abs()
+
+
+def bicubic_magnitudes(x, ho, wo):
+    """What the bound of the bicubic resize needs beside the value, [n, C, ho, wo] each: S = sum |wy| |wx| |x| over the 4 x 4 taps;
+    pos = the same sum with one axis' weights replaced by |dw/dt| times the source coordinate (an error of 2^-23 of the coordinate in t);
+    wgt = with one axis' weights replaced by the largest partial sum of its Horner evaluation (36 outer taps, 4.5 inner)."""
+    n, C, H, W = x.shape
+    ax = d(x).abs()
+    dev = x.device
+
+    def axis(size, out):
+        r = (size - 1) / (out - 1) if out > 1 else 0.0
+        f = torch.arange(out, dtype=torch.float64, device=dev) * r
+        i = torch.floor(f)
+        w, dw = _cubic(f - i)
+        idx = (i.to(torch.int64)[:, None] + torch.arange(-1, 3, device=dev)[None]).clamp(0, size - 1)
+        # a coordinate that fp32 puts on the other side of an integer: the weights are continuous there, the bound holds either way
+        return idx, w, dw * f[:, None], torch.tensor([36.0, 4.5, 4.5, 36.0], dtype=torch.float64, device=dev).expand(out, 4)
+    iy, wy, py, ey = axis(H, ho)
+    ix, wx, px, ex = axis(W, wo)
+    g = ax[:, :, iy][:, :, :, :, ix]                      # [n, C, ho, 4, wo, 4]
+    comb = lambda a, b: torch.einsum("ncyaxb,ya,xb->ncyx", g, a, b)
+    return comb(wy, wx), comb(py, wx) + comb(wy, px), comb(ey, wx) + comb(wy, ex)

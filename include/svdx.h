@@ -62,7 +62,7 @@ typedef struct svdx_gather {
 
 /* ABI revision of this header: bumped whenever an entry changes its argument list or meaning (100 = rounds 1-3; 400 = round 4).
  * svdx_version() returns the value the library was built with; the ctypes binding refuses a library whose number differs. */
-#define SVDX_VERSION 610
+#define SVDX_VERSION 611
 int         svdx_version(void);
 int         svdx_last_error(char* buf, size_t n);
 /* 1 when the binary was built for gfx950 and a device is usable */
@@ -87,6 +87,10 @@ int svdx_gemm(const void* A, const void* B, void* C, int M, int N, int K, int ld
               const void* res, int ldres, const svdx_gather* gather, const void* zero_page,
               int out_mode, float alpha, int split_k, int variant, int epilogue, const void* aux_in, void* aux_out, int aux_dim,
               int dtype, void* stream);
+/* Pure query (no device): the tile svdx_gemm launches for these arguments -- an id from the list above, 0 for the 64-bit-addressing kernel
+ * (variants 0 / 1), negative for an unknown variant.  geom (may be NULL), when a tile was resolved: {rows a tile owns, rows it computes,
+ * columns, LDS stages, waves, 1 when the tile has the second-operand loop of svdx_gemm_dual}.  svd_xtend_amd/ops.py mirrors it (GEMM_TILES). */
+int svdx_gemm_tile(int variant, int M, int N, int split_k, int epilogue, int aux_dim, int* geom);
 
 /* svdx_gemm with activation output, PLUS the GroupNorm statistics of the tensor it writes: gn_stats (the opaque buffer of svdx_gn_stats,
  * zeroed by the caller) receives sum / sum of squares of the ROUNDED results per (sample, group), sample = m / gn_rows, group =

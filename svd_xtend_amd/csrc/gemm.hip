@@ -18,6 +18,7 @@
 // (consecutive tiles of one A row-panel stay on one XCD's L2); split-K into float slabs + svdx_gemm_finalize.
 #include <stdlib.h>
 #include "common.h"
+#include "gemm_tiles.h"
 
 namespace {
 
@@ -1894,18 +1895,38 @@ __global__ void timestep_embed_kernel(const float* t, float* out, int n, int dim
     out[(size_t)i * dim + half + j] = sinf(a);
 }
 
+// raises a kernel's dynamic-LDS limit; the launchers call it once per instantiation, through a function-local static
+template <typename Kernel>
+bool allow_lds(Kernel* kernel, int bytes) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return true;
+}
+
 template <typename T>
 int launch_gemm(const GemmParams& p, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<T>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
-        attr_set = true;
-    }
+    [[maybe_unused]] static const bool lds_ok = allow_lds(&gemm_kernel<T>, 2 * STAGE_BYTES);
     dim3 grid(p.tiles_m * p.tiles_n, p.split_k);
     hipLaunchKernelGGL((gemm_kernel<T>), grid, dim3(NTHREADS), 2 * STAGE_BYTES, st, p);
     SVDX_LAUNCH_CHECK("svdx_gemm");
     return 0;
+}
+
+// XCDs as an (xcds / xn) x xn grid over tiles_m x tiles_n tiles, each owning cdiv(tiles_m, xcds / xn) x cdiv(tiles_n, xn) of them: -> the xn
+// with the least operand re-fetch (`cost`: every XCD column re-fetches A, every XCD row re-fetches B) among those that keep >= 90 % of
+// the best tile balance
+static int xcd_arrangement(int tiles_m, int tiles_n, int xcds, double a_bytes, double b_bytes, double& best_cost) {
+    int best_xn = 0;
+    double best_eff = 0;
+    best_cost = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int xn = 1; xn <= xcds; xn *= 2) {
+            const int xm = xcds / xn, sm = cdiv(tiles_m, xm), sn = cdiv(tiles_n, xn);
+            const double eff = (double)tiles_m * tiles_n / ((double)xcds * sm * sn);
+            if (pass == 0) { best_eff = eff > best_eff ? eff : best_eff; continue; }
+            const double cost = a_bytes * xn + b_bytes * xm;
+            if (eff >= 0.9 * best_eff && (best_xn == 0 || cost < best_cost)) { best_xn = xn; best_cost = cost; }
+        }
+    return best_xn;
 }
 
 // Tile counts, vector-store eligibility and the XCD arrangement of a BMT x BNT tile grid (see v4_tile_of_block): the arrangement with the
@@ -1922,16 +1943,8 @@ static int arrange_nt_grid(GemmParams& p, int BMT, int BNT, dim3& grid, int rows
     p.vec_ok = (p.ldc % 4 == 0) && (((uintptr_t)p.C & 15) == 0) && (!p.res || (p.ldres % 4 == 0 && ((uintptr_t)p.res & 15) == 0));
     const double a_bytes = 2.0 * p.M * (p.g.mode == SVDX_GATHER_PLAIN ? p.K : 2 * p.g.cin);   // conv: unique rows + halo
     const double b_bytes = 2.0 * (p.epi == SVDX_EPI_GEGLU_FWD ? 2 * p.aux_dim : p.N) * p.K;
-    int best_xn = 0;
-    double best_cost = 0, best_eff = 0;
-    for (int pass = 0; pass < 2; ++pass)
-        for (int xn = 1; xn <= 8; xn *= 2) {
-            const int xm = 8 / xn, sm = cdiv(p.tiles_m, xm), sn = cdiv(p.tiles_n, xn);
-            const double eff = (double)p.tiles_m * p.tiles_n / (8.0 * sm * sn);
-            if (pass == 0) { best_eff = eff > best_eff ? eff : best_eff; continue; }
-            const double cost = a_bytes * xn + b_bytes * xm;
-            if (eff >= 0.9 * best_eff && (best_xn == 0 || cost < best_cost)) { best_xn = xn; best_cost = cost; }
-        }
+    double best_cost, zb_cost;
+    const int best_xn = xcd_arrangement(p.tiles_m, p.tiles_n, 8, a_bytes, b_bytes, best_cost);
     p.xcd_n = best_xn;
     p.z_xcd = 0;
     int gx = p.tiles_m * p.tiles_n, gy = p.split_k;
@@ -1943,16 +1956,7 @@ static int arrange_nt_grid(GemmParams& p, int BMT, int BNT, dim3& grid, int rows
     // K slices on XCDs of their own (see v4_tile_of_block): among the arrangements of the 8 / split_k XCDs of a slice, the least re-fetch that keeps
     // >= 90 % of the best balance; taken when it fetches less than the slice-agnostic arrangement and leaves no more workgroup slots empty
     if (best_xn > 0 && (p.split_k == 2 || p.split_k == 4 || p.split_k == 8)) {
-        const int xps = 8 / p.split_k;
-        int zb_xn = 0; double zb_cost = 0, zb_eff = 0;
-        for (int pass = 0; pass < 2; ++pass)
-            for (int xn = 1; xn <= xps; xn *= 2) {
-                const int xm = xps / xn, sm = cdiv(p.tiles_m, xm), sn = cdiv(p.tiles_n, xn);
-                const double eff = (double)p.tiles_m * p.tiles_n / ((double)xps * sm * sn);
-                if (pass == 0) { zb_eff = eff > zb_eff ? eff : zb_eff; continue; }
-                const double cost = a_bytes * xn + b_bytes * xm;
-                if (eff >= 0.9 * zb_eff && (zb_xn == 0 || cost < zb_cost)) { zb_xn = xn; zb_cost = cost; }
-            }
+        const int xps = 8 / p.split_k, zb_xn = xcd_arrangement(p.tiles_m, p.tiles_n, xps, a_bytes, b_bytes, zb_cost);
         const int zsm = cdiv(p.tiles_m, xps / zb_xn), zsn = cdiv(p.tiles_n, zb_xn);
         if (zb_cost < best_cost && zsm * zsn <= p.sub_m * p.sub_n * p.split_k) {
             p.z_xcd = 1; p.xcd_n = zb_xn; p.sub_m = zsm; p.sub_n = zsn;
@@ -1971,15 +1975,8 @@ int launch_gemm_v4(GemmParams p, hipStream_t st) {
     constexpr int LDS_STG = NSTG * (BMT + BNT) * BK * 2, LDS_EPI = ((BMT * (BNT + 8) * 2 + 15) & ~15) + GN_LDS;      // K-loop stages | the rounded output tile parked for the coalesced stores (+ the GroupNorm statistics table behind it)
     constexpr int LDS = LDS_STG > LDS_EPI ? LDS_STG : LDS_EPI;
     static_assert(LDS <= 160 * 1024, "stages (and the epilogue tile parked in them) must fit the 160 KiB LDS");
-    constexpr bool HAS_DUAL = WGM == 2 && NSTG == 2;            // the LoRA second-operand loop is only instantiated for the round-1 tiles
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_v4_kernel<T, NB, MB, false, WGM, NSTG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (HAS_DUAL)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_v4_kernel<T, NB, MB, HAS_DUAL, WGM, NSTG>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
-    if (p.K2 > 0 && !HAS_DUAL) { svdx_set_error("svdx_gemm_dual: this tile variant has no second-operand loop"); return -2; }
+    constexpr bool HAS_DUAL = WGM == 2 && NSTG == 2;            // the LoRA second-operand loop is only instantiated for the round-1 tiles (gemm_entry refuses K2 > 0 on the others)
+    [[maybe_unused]] static const bool lds_ok = allow_lds(&gemm_v4_kernel<T, NB, MB, false, WGM, NSTG>, LDS) && (!HAS_DUAL || allow_lds(&gemm_v4_kernel<T, NB, MB, HAS_DUAL, WGM, NSTG>, LDS));
     dim3 grid;
     p.m_step = STEP;
     if (int rc = arrange_nt_grid(p, STEP, BNT, grid, BMT)) return rc;
@@ -1996,12 +1993,7 @@ int launch_gemm_v5(GemmParams p, hipStream_t st) {
     constexpr int LDS_STG = 2 * (BMT + BNT) * BK * 2, LDS_EPI = ((BMT * (BNT + 8) * 2 + 15) & ~15) + GN_LDS;
     constexpr int LDS = LDS_STG > LDS_EPI ? LDS_STG : LDS_EPI;
     static_assert(LDS <= 160 * 1024, "K-tiles (and the epilogue tile parked in them) must fit the 160 KiB LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_v5_kernel<T, MF, NF>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
-    if (p.K2 > 0) { svdx_set_error("svdx_gemm_dual: this tile variant has no second-operand loop"); return -2; }
+    [[maybe_unused]] static const bool lds_ok = allow_lds(&gemm_v5_kernel<T, MF, NF>, LDS);
     dim3 grid;
     p.m_step = BMT;
     if (int rc = arrange_nt_grid(p, BMT, BNT, grid)) return rc;
@@ -2019,16 +2011,9 @@ static long tn_arrange(GemmParams& p) {
     }
     const int xps = 8 / p.split_k;
     const double a_bytes = 2.0 * p.K * p.M, b_bytes = 2.0 * p.K * p.N;          // dY [R, N_out] and X [R, K_out] of one call (p.M / p.N = output rows / columns)
-    int best_xn = 1;
-    double best_cost = 0, best_eff = 0;
-    for (int pass = 0; pass < 2; ++pass)
-        for (int xn = 1; xn <= xps; xn *= 2) {
-            const int xm = xps / xn, sm = cdiv(p.tiles_m, xm), sn = cdiv(p.tiles_n, xn);
-            const double eff = (double)p.tiles_m * p.tiles_n / ((double)xps * sm * sn);
-            if (pass == 0) { best_eff = eff > best_eff ? eff : best_eff; continue; }
-            const double cost = a_bytes * xn + b_bytes * xm;                     // every XCD column re-fetches dY, every XCD row re-fetches X
-            if (eff >= 0.9 * best_eff && (best_cost == 0 || cost < best_cost)) { best_xn = xn; best_cost = cost; }
-        }
+    double cost;                                                                // every XCD column re-fetches dY, every XCD row re-fetches X
+    int best_xn = xcd_arrangement(p.tiles_m, p.tiles_n, xps, a_bytes, b_bytes, cost);
+    if (best_xn == 0) best_xn = 1;
     p.xcd_n = best_xn;
     p.sub_m = cdiv(p.tiles_m, xps / best_xn);
     p.sub_n = cdiv(p.tiles_n, best_xn);
@@ -2038,11 +2023,7 @@ static long tn_arrange(GemmParams& p) {
 template <typename T, int NSTG, bool BUF = false>
 int launch_gemm_tn(GemmParams p, hipStream_t st) {
     constexpr int LDS = NSTG * STAGE_BYTES;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<T, NSTG, BUF>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
+    [[maybe_unused]] static const bool lds_ok = allow_lds(&gemm_tn_kernel<T, NSTG, BUF>, LDS);
     dim3 grid((unsigned)tn_arrange(p));
     hipLaunchKernelGGL((gemm_tn_kernel<T, NSTG, BUF>), grid, dim3(NTHREADS), LDS, st, p);
     SVDX_LAUNCH_CHECK("svdx_gemm_tn");
@@ -2053,11 +2034,7 @@ template <typename T, int PA, int PB, int NSTG, bool BUF = false>
 int launch_gemm_tn8(GemmParams p, hipStream_t st) {
     constexpr int LDS = NSTG * (PA + PB) * 64 * 256;
     static_assert(LDS <= 160 * 1024, "stages must fit the 160 KiB LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn8_kernel<T, PA, PB, NSTG, BUF>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
+    [[maybe_unused]] static const bool lds_ok = allow_lds(&gemm_tn8_kernel<T, PA, PB, NSTG, BUF>, LDS);
     p.tiles_m = cdiv(p.M, 128 * PA);
     p.tiles_n = cdiv(p.N, 128 * PB);
     dim3 grid((unsigned)tn_arrange(p));
@@ -2109,6 +2086,19 @@ extern "C" int svdx_gemm_tn(const void* A, const void* B, float* C, int R, int N
     });
 }
 
+extern "C" int svdx_gemm_tile(int variant, int M, int N, int split_k, int epilogue, int aux_dim, int* geom) {
+    const int id = resolve_tile(variant, M, N, split_k, epilogue, aux_dim);
+    const GemmTile* t = gemm_tile(id);
+    if (geom && t) {
+        geom[0] = t->row_step; geom[1] = t->rows; geom[2] = t->cols; geom[3] = t->stages; geom[4] = t->waves; geom[5] = t->has_dual;
+    }
+    return id;
+}
+
+// the launch of one row of SVDX_GEMM_TILES, as a case of gemm_entry's switch over the resolved tile
+#define SVDX_LAUNCH_V4(id, sib, NB, MB, WGM, NSTG, MSTEP) case id: return launch_gemm_v4<T, NB, MB, WGM, NSTG, MSTEP>(p, st);
+#define SVDX_LAUNCH_V5(id, sib, MF, NF) case id: return launch_gemm_v5<T, MF, NF>(p, st);
+
 static int gemm_entry(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
                       const float* bias, const float* rowvec, int rv_ld, int rv_rows_per_group, int rv_mod,
                       const void* res, int ldres, const svdx_gather* gather, const void* zero_page,
@@ -2116,6 +2106,8 @@ static int gemm_entry(const void* A, const void* B, void* C, int M, int N, int K
                       int aux_dim, const void* A2, const void* B2, int K2, int lda2, int ldb2, int a2_seg, float* gn_stats, int gn_rows,
                       int gn_cg, int dtype, void* stream) {
     SVDX_CHECK_ARG(A && B && C, "svdx_gemm: null operand");
+    const int tile_id = resolve_tile(variant, M, N, split_k, epilogue, aux_dim);
+    const GemmTile* tile = gemm_tile(tile_id);                   // null: the 64-bit-pointer kernel (variants 0 / 1) or an unknown variant
     if (gn_stats) {
         SVDX_CHECK_ARG(variant >= 2 && out_mode == SVDX_OUT_ACT && split_k == 1 && epilogue == SVDX_EPI_NONE && K2 <= 0,
                        "svdx_gemm_gn: statistics ride on an unsplit variant-4 launch with activation output and no fused epilogue");
@@ -2126,9 +2118,9 @@ static int gemm_entry(const void* A, const void* B, void* C, int M, int N, int K
         SVDX_CHECK_ARG(A2 && B2 && K2 % BK == 0 && lda2 % 8 == 0 && ldb2 % 8 == 0 && lda2 >= K2 && ldb2 >= K2 &&
                            (((uintptr_t)A2 | (uintptr_t)B2) & 15) == 0, "svdx_gemm_dual: second operand pair misaligned (K2=%d)", K2);
         SVDX_CHECK_ARG(variant >= 2 && split_k == 1, "svdx_gemm_dual: needs variant 4 and split_k == 1");
-        const int bn = (variant != 8 && N % 160 == 0) ? 160 : 128;           // tile width the dispatch below will pick
-        SVDX_CHECK_ARG(a2_seg == 0 || (a2_seg > 0 && N % a2_seg == 0 && a2_seg % bn == 0 && lda2 >= (N / a2_seg) * K2),
-                       "svdx_gemm_dual: a2_seg_n=%d must divide N=%d, be a multiple of the %d-column tile, and fit lda2", a2_seg, N, bn);
+        SVDX_CHECK_ARG(!tile || tile->has_dual, "svdx_gemm_dual: this tile variant has no second-operand loop");
+        SVDX_CHECK_ARG(!tile || a2_seg == 0 || (a2_seg > 0 && N % a2_seg == 0 && a2_seg % tile->cols == 0 && lda2 >= (N / a2_seg) * K2),
+                       "svdx_gemm_dual: a2_seg_n=%d must divide N=%d, be a multiple of the %d-column tile, and fit lda2", a2_seg, N, tile ? tile->cols : 0);
     }
     if (epilogue != SVDX_EPI_NONE) {
         SVDX_CHECK_ARG(variant >= 2 && out_mode == SVDX_OUT_ACT && split_k == 1 && !res && !rowvec && aux_dim > 0 && aux_dim % 64 == 0 &&
@@ -2211,56 +2203,12 @@ static int gemm_entry(const void* A, const void* B, void* C, int M, int N, int K
     DISPATCH_DTYPE(dtype, {
         if (variant >= 2 && a_bytes > 0 && b_bytes > 0) {
             p.a_bytes = (int)a_bytes; p.b_bytes = (int)b_bytes;
-            // tile choice: variant 4 = heuristic; 6 / 7 / 8 force 160x160 / 128x160 / 128x128 (the host autotuner times them)
-            const bool nb5 = epilogue == SVDX_EPI_GEGLU_FWD || variant == 8 || variant == 17 || variant == 18 || variant == 21 || variant == 22 || variant == 24 || variant == 26 || variant == 27 ? false : (N % 160 == 0);
+            if (!tile) { svdx_set_error("svdx_gemm: unknown variant %d", variant); return -2; }
             // the GEGLU-backward epilogue only exists in the coalesced store path, which takes whole column tiles: d(pre) of a partial last
             // tile would be written as plain d(h) (found by tests/sim/fuzz.py; F = 4C of the UNet is always a multiple of 128)
-            SVDX_CHECK_ARG(epilogue != SVDX_EPI_GEGLU_BWD || N % (nb5 ? 160 : 128) == 0,
-                           "svdx_gemm: GEGLU bwd with tile variant %d needs N=%d to be a multiple of its %d-column tile", variant, N, nb5 ? 160 : 128);
-            // 160-row tiles when they turn a 1.1-wave grid (512 resident blocks) into a single wave, e.g. M = 35840, N = 320:
-            // 280 x 2 = 560 tiles of 128 rows vs 224 x 2 = 448 tiles of 160 rows
-            const long t128 = (long)cdiv(M, 128) * cdiv(N, 160), t160 = (long)cdiv(M, 160) * cdiv(N, 160);
-            const bool mb5 = nb5 && ((variant == 6) ||
-                                     (variant == 4 && split_k == 1 && (cdiv(t128, 512) * 4 > cdiv(t160, 512) * 5) && t160 >= 384));
-            if (variant >= 16) {
-                // ring-staged tiles (see the K-loop banner), one workgroup per CU:
-                //   16: 256x160, 3 stages, eight waves   17: 256x128, 3 stages, eight waves   18: 256x256, 2 stages, eight waves
-                //   20: 128x160, 4 stages, four waves    21: 128x128, 4 stages, four waves
-                //   23: 192x160, 3 stages, eight waves   22: 192x128, 3 stages, eight waves  (M = 8960: 47 row tiles x 5 = 235 of 256 CUs
-                //                                                                             where 256-row tiles give 175)
-                //   25:  96x160, 4 stages, four waves    24:  96x128, 4 stages, four waves   (M = 2240, N = 1280, short K: 240 tiles, not 180)
-                //   26: 192x128, TWO stages, eight waves: 80 KB of LDS and 114 VGPRs, so TWO workgroups share a CU -- the tile under the GEGLU
-                //       epilogues, where main loop, GELU polynomial and 275-366 MB of stores run one after the other inside a workgroup
-                //   28: 128x160, 27: 128x128, TWO stages, eight waves (72 / 64 KB of LDS: two workgroups per CU): candidates of the in-situ
-                //       tuner for the short-K linears, not yet in the cost model (no measured rate)
-                // A 160-wide request on an N that 160 does not divide (or with the GEGLU-forward epilogue) takes the 128-wide sibling;
-                // 256-wide tiles need N % 256 == 0 (their GEGLU epilogues have no partial column tile).
-                const int n_cols = epilogue == SVDX_EPI_GEGLU_FWD ? 2 * aux_dim : N;
-                // Two-role tiles (gemm_v5_kernel, round 6), one workgroup per CU:   32: 256x256   34: 160x320.  Their GEGLU epilogues take whole
-                // column tiles; a request that does not divide runs the ring tiles' 160- / 128-wide siblings instead (like 18 -> 17 below).
-                if (variant == 32 && (epilogue == SVDX_EPI_NONE || n_cols % 256 == 0)) return launch_gemm_v5<T, 8, 4>(p, st);
-                if (variant == 34 && (epilogue == SVDX_EPI_NONE || n_cols % 320 == 0)) return launch_gemm_v5<T, 5, 5>(p, st);
-                if (variant == 32 || variant == 34) variant = 16;
-                // 36 (round 6): 144 x 160, SIX waves (3 x 2), two stages, two workgroups per CU, row tiles 140 apart -- the 64x40 level's
-                //     35840 rows are 256 x 140 and the 32x20 level's 8960 are 64 x 140, so N = 320 / 1280 give exactly 512 workgroups: every
-                //     slot of the chip, where the 160-row tile of variant 6 fills 448 of them.  160-wide only; no GEGLU-forward epilogue.
-                if (variant == 36) {
-                    if (nb5 && epilogue != SVDX_EPI_GEGLU_FWD) return launch_gemm_v4<T, 5, 3, 3, 2, 140>(p, st);
-                    variant = 28;
-                }
-                switch (variant) {
-                    case 18: if (n_cols % 256 == 0) return launch_gemm_v4<T, 8, 4, 4, 2>(p, st);   // else: fall through to 256 x 128
-                    case 16: case 17: return nb5 ? launch_gemm_v4<T, 5, 4, 4, 3>(p, st) : launch_gemm_v4<T, 4, 4, 4, 3>(p, st);
-                    case 20: case 21: return nb5 ? launch_gemm_v4<T, 5, 4, 2, 4>(p, st) : launch_gemm_v4<T, 4, 4, 2, 4>(p, st);
-                    case 22: case 23: return nb5 ? launch_gemm_v4<T, 5, 3, 4, 3>(p, st) : launch_gemm_v4<T, 4, 3, 4, 3>(p, st);
-                    case 26: return launch_gemm_v4<T, 4, 3, 4, 2>(p, st);
-                    case 27: case 28: return nb5 ? launch_gemm_v4<T, 5, 2, 4, 2>(p, st) : launch_gemm_v4<T, 4, 2, 4, 2>(p, st);
-                    case 24: case 25: return nb5 ? launch_gemm_v4<T, 5, 3, 2, 4>(p, st) : launch_gemm_v4<T, 4, 3, 2, 4>(p, st);
-                    default: svdx_set_error("svdx_gemm: unknown variant %d", variant); return -2;
-                }
-            }
-            if (mb5) return launch_gemm_v4<T, 5, 5>(p, st);
-            return nb5 ? launch_gemm_v4<T, 5, 4>(p, st) : launch_gemm_v4<T, 4, 4>(p, st);
+            SVDX_CHECK_ARG(epilogue != SVDX_EPI_GEGLU_BWD || N % tile->cols == 0,
+                           "svdx_gemm: GEGLU bwd with tile variant %d needs N=%d to be a multiple of its %d-column tile", variant, N, tile->cols);
+            switch (tile_id) { SVDX_GEMM_TILES(SVDX_LAUNCH_V4, SVDX_LAUNCH_V5) }
         }
         if (epilogue != SVDX_EPI_NONE) { svdx_set_error("svdx_gemm: fused epilogue unavailable (buffer too large for variant 4)"); return -2; }
         if (gn_stats) { svdx_set_error("svdx_gemm_gn: statistics unavailable (buffer too large for variant 4)"); return -2; }

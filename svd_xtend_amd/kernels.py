@@ -26,7 +26,7 @@ LN_PARTIAL_ROWS = 2048
 GN_REPLICAS = 8
 GN_STAT_FLOATS = 4             # floats of storage per (replica, sample, group) of a GroupNorm statistics buffer: two int64
 GATHER_PLAIN, GATHER_CONV3X3, GATHER_CONV3X3_DGRAD2, GATHER_TEMPORAL3, GATHER_CONV3X3_PAD0 = 0, 1, 2, 3, 4
-ABI_VERSION = 610              # include/svdx.h: SVDX_VERSION this binding was written against
+ABI_VERSION = 611              # include/svdx.h: SVDX_VERSION this binding was written against
 OPT_STATE_FLOATS = 16          # include/svdx.h: layout of the optimizer / loss-scale / schedule state
 SCHED_KINDS = {"constant": 0, "constant_with_warmup": 1, "linear": 2, "cosine": 3, "cosine_with_restarts": 4, "polynomial": 5, "piecewise_constant": 6}
 SCHED_MAX_RULES = 8            # include/svdx.h SVDX_SCHED_MAX_RULES: step rules of piecewise_constant, stored behind the 16 state floats
@@ -153,7 +153,7 @@ _SIGS = {
 }
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "d": ctypes.c_double, "l": ctypes.c_int64, "z": ctypes.c_size_t}
 
-EXPORTED_SYMBOLS = tuple(_SIGS) + ("svdx_wall_clock_khz", "svdx_version", "svdx_last_error", "svdx_device_ok", "svdx_tsa_pixels_per_band", "svdx_ln_bwd_blocks",
+EXPORTED_SYMBOLS = tuple(_SIGS) + ("svdx_wall_clock_khz", "svdx_version", "svdx_last_error", "svdx_device_ok", "svdx_tsa_pixels_per_band", "svdx_ln_bwd_blocks", "svdx_gemm_tile",
                                     "svdx_plan_launches", "svdx_plan_bytes")
 PARAMS_F32, PARAMS_BF16_REFERENCE = 0, 1      # include/svdx.h: param_mode of svdx_adamw / svdx_adamw_tiled
 TN_FLAT = 64                   # include/svdx.h SVDX_TN_FLAT: the staging of operands >= 2 GiB, on request (tests)
@@ -203,6 +203,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.svdx_tsa_pixels_per_band.restype = ctypes.c_int
     lib.svdx_ln_bwd_blocks.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.svdx_ln_bwd_blocks.restype = ctypes.c_int
+    lib.svdx_gemm_tile.argtypes = [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)]
+    lib.svdx_gemm_tile.restype = ctypes.c_int
     for name in ("svdx_plan_launches", "svdx_plan_bytes"):
         getattr(lib, name).argtypes = [ctypes.c_void_p]
         getattr(lib, name).restype = ctypes.c_int64

@@ -13,7 +13,7 @@ import contextlib
 import functools
 import os
 from types import SimpleNamespace
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -259,26 +259,47 @@ def choose_split(rt: "Runtime", M: int, N: int, Kd: int, ldc: int, bn: int = 0) 
     return split
 
 
-# svdx_gemm tile variants (csrc/gemm.hip): rows x columns of the output tile, LDS stages of the K-loop, waves per workgroup
-TILE_OF_VARIANT = {7: (128, 160, 2, 4), 6: (160, 160, 2, 4), 8: (128, 128, 2, 4),
-                   16: (256, 160, 3, 8), 17: (256, 128, 3, 8), 18: (256, 256, 2, 8), 20: (128, 160, 4, 4), 21: (128, 128, 4, 4),
-                   23: (192, 160, 3, 8), 22: (192, 128, 3, 8), 25: (96, 160, 4, 4), 24: (96, 128, 4, 4)}
-# instantiated in csrc/gemm.hip and offered to the in-situ tuner (bench.py --tune), but not to the cost model:
+class Tile(NamedTuple):
+    """One output tile of svdx_gemm (csrc/gemm_tiles.h holds the same list; tests pin the two together through svdx_gemm_tile)."""
+    step: int                  # rows a tile owns: what tile counts follow
+    rows: int                  # rows it computes
+    cols: int
+    stages: int                # LDS stages of the K-loop
+    waves: int                 # waves per workgroup
+    sib: Optional[int]         # the narrower tile a request falls to when its columns do not fit N
+    rate: Optional[float]      # TFLOP/s one CU sustains on the tile's K-loop when the CU is full (8192^3 runs of tools/ring_check.py divided by
+    #                            256 CUs, trimmed by the in-situ sweeps of bench.py --tune): the two-stage four-wave tiles need two workgroups
+    #                            per CU for it.  None: not in the cost model
+
+
+GEGLU_TWO_PER_CU = 26      # 192 x 128, eight waves, two stages: 80 KB of LDS, two workgroups per CU (csrc/gemm.hip); used under GEGLU epilogues only
+
+# Rows with a rate are what the cost model (choose_cfg) searches.  Rows without one are instantiated in csrc/gemm.hip and offered to the
+# in-situ tuner (bench.py --tune) only -- except GEGLU_TWO_PER_CU, which geglu_candidates adds under the fused epilogues:
 #   27 / 28: two-stage eight-wave tiles without a measured rate;
 #   32 / 34: round 6's two-role eight-wave tiles (gemm_v5_kernel: 256 x 256 and 160 x 320).  Isolated they are the fastest kernels of the library
 #   (8192^3: 1397 TF/s against 1297 for tile 18; the 64x40-level convolutions 5-20 % ahead of tile 6), inside the step they only TIE with
 #   the two-per-CU four-wave tiles (in-situ sweep: +-3 % per problem, one problem -10 %; cost-model selection +0.45 ms / step):
 #   profiles/r6e_tune_dump_reworked.txt, DESIGN.md 6.4.  A 160 x 320 two-role workgroup IS two 160 x 160 workgroups side by side.
+#   They take partial column tiles (no sibling), except under a GEGLU epilogue, where the library runs 16 / 17 instead.
 #   36: round 6's 144 x 160 SIX-wave two-stage tile whose row tiles are 140 apart (two workgroups per CU): 35840 = 256 x 140 and 8960 = 64 x 140,
 #   so N = 320 at the 64x40 level / N = 1280 at the 32x20 level launch exactly 512 workgroups -- every slot of the chip -- where the
-#   160-row tile of variant 6 fills 448.  The entry's first number is the row STEP (what tile counts follow); it computes 144 rows.
+#   160-row tile of variant 6 fills 448.
 #   Isolated it is 3-12 % ahead of tile 6 on the N = 320 problems of the 64x40 level (profiles/r6m_ring_time_tile36.txt); selected for every
 #   (1, 6) choice whose grid it fills in one round it moved the step by -0.07 ms (profiles/r6n_ab_tile36.txt: 48.01 against 48.08 ms) -- inside the
 #   step those launches wait for their cold operands, not for workgroup slots.  A tuner candidate only.
-STAGED_TILES = {27: (128, 128, 2, 8), 28: (128, 160, 2, 8), 32: (256, 256, 2, 8), 34: (160, 320, 2, 8), 36: (140, 160, 2, 6)}
-# TFLOP/s one CU sustains on a variant's K-loop when the CU is full (8192^3 runs of tools/ring_check.py divided by 256 CUs, trimmed by
-# the in-situ sweeps of bench.py --tune): the two-stage four-wave tiles need two workgroups per CU for it
-_TILE_RATE = {6: 4.05, 7: 3.5, 8: 3.5, 16: 4.4, 17: 4.0, 18: 3.6, 20: 2.75, 21: 2.5, 22: 3.8, 23: 3.8, 24: 2.4, 25: 2.05}
+GEMM_TILES = {7: Tile(128, 128, 160, 2, 4, 8, 3.5), 6: Tile(160, 160, 160, 2, 4, 8, 4.05), 8: Tile(128, 128, 128, 2, 4, None, 3.5),
+              16: Tile(256, 256, 160, 3, 8, 17, 4.4), 17: Tile(256, 256, 128, 3, 8, None, 4.0), 18: Tile(256, 256, 256, 2, 8, 17, 3.6),
+              20: Tile(128, 128, 160, 4, 4, 21, 2.75), 21: Tile(128, 128, 128, 4, 4, None, 2.5),
+              23: Tile(192, 192, 160, 3, 8, 22, 3.8), 22: Tile(192, 192, 128, 3, 8, None, 3.8),
+              25: Tile(96, 96, 160, 4, 4, 24, 2.05), 24: Tile(96, 96, 128, 4, 4, None, 2.4),
+              GEGLU_TWO_PER_CU: Tile(192, 192, 128, 2, 8, None, None),
+              27: Tile(128, 128, 128, 2, 8, None, None), 28: Tile(128, 128, 160, 2, 8, 27, None),
+              32: Tile(256, 256, 256, 2, 8, None, None), 34: Tile(160, 160, 320, 2, 8, None, None), 36: Tile(140, 144, 160, 2, 6, 28, None)}
+# the two sets by name, as (row step, columns, stages, waves): what the cost model searches | what only the in-situ tuner is offered
+TILE_OF_VARIANT = {v: (t.step, t.cols, t.stages, t.waves) for v, t in GEMM_TILES.items() if t.rate is not None}
+STAGED_TILES = {v: (t.step, t.cols, t.stages, t.waves) for v, t in GEMM_TILES.items() if t.rate is None and v != GEGLU_TWO_PER_CU}
+_DUAL_TILES = tuple(v for v, t in GEMM_TILES.items() if t.stages == 2 and t.waves == 4)     # the only tiles with the second-operand loop (LoRA)
 _ALONE, _FILL_STEPS, _EPI_US, _FIN_US, _FIN_BYTES_PER_US = 0.5, 1.5, 3.0, 12.0, 6.0e6
 
 
@@ -302,13 +323,12 @@ def estimate_gemm_us(M: int, N: int, Kd: int, split: int, variant: int, cin: int
     """Cost model behind `choose_cfg`: rounds of workgroups on the fullest XCD x (K-steps + pipeline fill) x time per K-step of the
     tile, + the epilogue, + the float-slab round trip of a split reduction.  Fitted to two in-situ sweeps of round 3 (108 problems of
     the 14 x 512 x 320 step: its picks cost 0.6 % more than the measured best of every problem)."""
-    bm, bn, stages, waves = TILE_OF_VARIANT[variant]
+    bm, _, bn, stages, waves, _, rate = GEMM_TILES[variant]
     Tm, Tn = -(-M // bm), -(-N // bn)
     two_stage = stages == 2 and waves == 4
     per_xcd = 64 if two_stage else 32                       # resident workgroups of one XCD's 32 CUs
     block = _xcd_block_tiles(Tm, Tn, 2.0 * M * (2 * cin if cin else Kd), 2.0 * N * Kd) * split
     rounds = -(-block // per_xcd)
-    rate = _TILE_RATE[variant]
     if two_stage:
         rate = rate / 2 if block > 32 else rate * _ALONE    # shares its CU | alone on it (a drained K-step is exposed latency)
     ksteps = -(-(Kd // 64) // split)
@@ -322,13 +342,11 @@ def _nt_candidates(M: int, N: int, Kd: int, splittable: bool, fused_epilogue: bo
     kt = (Kd + 63) // 64
     out = []
     for v, (bm, bn, _stages, waves) in list(TILE_OF_VARIANT.items()) + (list(STAGED_TILES.items()) if staged else []):
-        if bn == 160 and (N % 160 or fused_epilogue):       # the GEGLU-forward epilogue pairs 64 value with 64 gate columns: 128-wide tiles
+        if bn != 128 and N % bn:                            # wider tiles: whole column tiles only
+            continue
+        if bn == 160 and fused_epilogue:                    # the GEGLU-forward epilogue pairs 64 value with 64 gate columns: 128-wide tiles
             continue
         if bn == 128 and N % 160 == 0 and N % 128 and N > 160:
-            continue
-        if bn == 256 and N % 256:
-            continue
-        if bn == 320 and N % 320:
             continue
         if waves == 8 and M < 2 * bm:
             continue
@@ -342,7 +360,8 @@ def _nt_candidates(M: int, N: int, Kd: int, splittable: bool, fused_epilogue: bo
 
 def _dual_candidates(M: int, N: int, Kd: int):
     """The second-operand loop (LoRA) exists for the two-stage four-wave tiles only."""
-    return [(1, v) for v in ((7, 6, 8) if N % 160 == 0 and N % 128 == 0 else ((7, 6) if N % 160 == 0 else (8,)))]
+    wide = N % 160 == 0
+    return [(1, v) for v in _DUAL_TILES if (wide if GEMM_TILES[v].cols == 160 else not wide or N % 128 == 0)]
 
 
 def choose_cfg(rt: "Runtime", M: int, N: int, Kd: int, ldc: int, cin: int = 0, dual: bool = False):
@@ -367,9 +386,6 @@ def _choose_cfg_v4(split_k: bool, M: int, N: int, Kd: int, ldc: int, cin: int, d
     if not cands:
         return choose_split(SimpleNamespace(split_k=split_k), M, N, Kd, ldc), 4
     return min(cands, key=lambda c: estimate_gemm_us(M, N, Kd, c[0], c[1], cin))
-
-
-GEGLU_TWO_PER_CU = 26      # 192 x 128, eight waves, two stages: 80 KB of LDS, two workgroups per CU (csrc/gemm.hip); used under GEGLU epilogues only
 
 
 def geglu_candidates(M: int, N: int, Kd: int, fwd: bool = True):
@@ -474,11 +490,10 @@ def tuned_call(rt: "Runtime", key, make_cands, fallback, run) -> None:
 def gn_tile_ok(variant: int, N: int, rows: int, cg: int) -> bool:
     """Can the tile `variant` take GroupNorm statistics in its store loop (svdx_gemm_gn)?  Whole column tiles, and a tile that touches
     at most 8 samples and 36 groups (csrc/gemm.hip: GN_MAX_S / GN_MAX_G)."""
-    t = TILE_OF_VARIANT.get(variant) or STAGED_TILES.get(variant)
-    if t is None:
+    t = GEMM_TILES.get(variant)
+    if t is None or variant == GEGLU_TWO_PER_CU:             # (the GEGLU tile is no candidate of gemm_act)
         return False
-    bm, bn = (144 if variant == 36 else t[0]), t[1]          # (variant 36 steps 140 rows and computes 144: the launcher checks the height)
-    return N % bn == 0 and (bm - 1) // rows + 2 <= 8 and (bn - 1) // cg + 2 <= 36
+    return N % t.cols == 0 and (t.rows - 1) // rows + 2 <= 8 and (t.cols - 1) // cg + 2 <= 36     # (the launcher checks the height computed, not the step)
 
 
 def gemm_act(rt: "Runtime", A, B, out, M, N, Kd, lda, ldb, ldc, bias=None, rowvec=None, rv_ld=0, rv_rpg=0, rv_mod=0,
@@ -532,19 +547,14 @@ def gemm_act(rt: "Runtime", A, B, out, M, N, Kd, lda, ldb, ldc, bias=None, rowve
     return done[0]
 
 
-def _tile_launched(variant: int, M: int, N: int) -> int:
-    """The tile svdx_gemm resolves `variant` to (csrc/gemm.hip: variant 4 is a rule among 6 / 7 / 8; a 160-wide request on an N that 160
-    does not divide takes the 128-wide sibling, 256-wide tiles need N % 256 == 0)."""
+def _tile_launched(variant: int, M: int, N: int, split_k: int = 1) -> int:
+    """The tile svdx_gemm resolves `variant` to without a fused epilogue (csrc/gemm_tiles.h resolve_tile: variant 4 is a rule among 6 / 7 / 8;
+    a 160-wide request on an N that 160 does not divide takes the 128-wide sibling, the 256-wide ring tile needs N % 256 == 0)."""
     if variant == 4:
-        if N % 160:
-            return 8
-        t128, t160 = -(-M // 128) * (N // 160), -(-M // 160) * (N // 160)
-        return 6 if (-(-t128 // 512) * 4 > -(-t160 // 512) * 5 and t160 >= 384) else 7
-    sib = {16: 17, 23: 22, 25: 24, 20: 21, 28: 27, 7: 8, 6: 8, 36: 27}
-    if variant in sib and N % 160:
-        return sib[variant]
-    if variant == 18 and N % 256:
-        return 17
+        t128, t160 = -(-M // 128) * -(-N // 160), -(-M // 160) * -(-N // 160)
+        variant = 6 if (split_k == 1 and -(-t128 // 512) * 4 > -(-t160 // 512) * 5 and t160 >= 384) else 7
+    while variant in GEMM_TILES and N % GEMM_TILES[variant].cols and GEMM_TILES[variant].sib is not None:
+        variant = GEMM_TILES[variant].sib
     return variant
 
 

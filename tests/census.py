@@ -614,9 +614,8 @@ def coalesced_columns(a, C, res):
     epilogue A): the launch resolves to one of the four-/eight-wave tiles, C and the residual are 16-byte aligned with pitches that
     are multiples of 8, and the column tile is whole (n0 + BN <= N: a partial last tile takes the direct epilogue).  Every other
     element gets the residual in fp32 before its one rounding."""
-    from svd_xtend_amd.ops import TILE_OF_VARIANT, _tile_launched
-    width = {t: v[1] for t, v in TILE_OF_VARIANT.items()}
-    width.update({36: 160, 28: 160, 27: 128})            # the six-wave tile and the two-stage eight-wave tiles: the same kernel template
+    from svd_xtend_amd.ops import GEMM_TILES, _tile_launched
+    width = {v: t.cols for v, t in GEMM_TILES.items() if v not in (26, 32, 34)}      # the tiles gemm_act reaches through gemm_v4_kernel
     bn = width.get(_tile_launched(a["variant"], a["M"], a["N"]))
     if bn is None or a["ldc"] % 8 or C.data_ptr() % 16 or (res is not None and (a["ldres"] % 8 or res.data_ptr() % 16)):
         return 0

@@ -415,7 +415,7 @@ def check_small(P, dt):
 def check_gemm_gn(P, dt, variant):
     """svdx_gemm_gn: the GEMM result against the emulation, and the GroupNorm statistics it leaves against a statistics pass (emulated)
     over the tensor THE LAUNCH ITSELF wrote -- same rounded values, so only the fp32 summation order differs."""
-    from svd_xtend_amd.ops import TILE_OF_VARIANT, STAGED_TILES, _tile_launched, gn_tile_ok
+    from svd_xtend_amd.ops import _tile_launched, gn_tile_ok
     g = torch.Generator().manual_seed(11)
     res = []
     # (samples, rows per sample, N, channels per group, K, gather?)   -- 2-D norms over frames shorter / longer than a tile, a clip-wide norm

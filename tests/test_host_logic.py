@@ -387,40 +387,41 @@ def test_geglu_tile_rule():
 
 
 def test_tile_table_matches_the_kernel_dispatch():
-    """ops.TILE_OF_VARIANT (what the cost model believes a variant's tile is) against the template arguments csrc/gemm.hip dispatches that
-    variant to: rows = 16 * MB * WGM, columns = 32 * NB, stages = NSTG, waves = 2 * WGM."""
-    import os
-    import re
-    from svd_xtend_amd.ops import GEGLU_TWO_PER_CU, STAGED_TILES, TILE_OF_VARIANT
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "svd_xtend_amd", "csrc", "gemm.hip")).read()
-    seen = {}
-    for line in src.splitlines():
-        m = re.match(r"\s*((?:case \d+: )+)(.*)", line)
-        if not m or "launch_gemm_v4<" not in m.group(2):
-            continue
-        variants = [int(v) for v in re.findall(r"case (\d+):", m.group(1))]
-        tiles = [tuple(int(x) for x in t) for t in re.findall(r"launch_gemm_v4<T, (\d+), (\d+), (\d+), (\d+)>", m.group(2))]
-        assert tiles, line
-        for v in variants:
-            seen[v] = tiles
-    # the two-role tiles: `if (variant == V && ...) return launch_gemm_v5<T, MF, NF>(p, st);` -> rows = 32 * MF, columns = 64 * NF, two K-tiles, eight waves
-    for v, mf, nf in re.findall(r"if \(variant == (\d+) &&[^\n]*launch_gemm_v5<T, (\d+), (\d+)>", src):
-        seen[int(v)] = [("v5", int(mf), int(nf))]
-    # variant 36: `if (variant == 36) { if (...) return launch_gemm_v4<T, NB, MB, WGM, NSTG, MSTEP>(p, st);`: the table holds the row STEP, the tile computes 16 MB WGM rows
-    m36 = re.search(r"if \(variant == 36\) \{\s*if \([^\n]*launch_gemm_v4<T, (\d+), (\d+), (\d+), (\d+), (\d+)>", src)
-    assert m36, "variant 36 dispatch not found"
-    nb, mb, wgm, nstg, mstep = (int(x) for x in m36.groups())
-    assert STAGED_TILES[36] == (mstep, 32 * nb, nstg, 2 * wgm) and mstep <= 16 * mb * wgm == 144
-    assert not set(STAGED_TILES) & set(TILE_OF_VARIANT)
-    for v, (bm, bn, stages, waves) in list(TILE_OF_VARIANT.items()) + [kv for kv in STAGED_TILES.items() if kv[0] != 36]:
-        if v < 16:
-            continue                                   # 6 / 7 / 8: the two-stage four-wave defaults of launch_gemm_v4<T, NB, MB>
-        if seen[v][0][0] == "v5":
-            geo = {(32 * mf, 64 * nf, 2, 8) for _, mf, nf in seen[v]}
-        else:
-            geo = {(16 * mb * wgm, 32 * nb, nstg, 2 * wgm) for nb, mb, wgm, nstg in seen[v]}
-        assert (bm, bn, stages, waves) in geo, (v, (bm, bn, stages, waves), geo)
-    assert {(16 * mb * wgm, 32 * nb, nstg, 2 * wgm) for nb, mb, wgm, nstg in seen[GEGLU_TWO_PER_CU]} == {(192, 128, 2, 8)}
+    """ops.GEMM_TILES / ops._tile_launched (what the host believes a variant's tile is) against the built library's own answer,
+    svdx_gemm_tile: the tile every variant id resolves to and the geometry its launch was instantiated with (csrc/gemm_tiles.h)."""
+    import ctypes
+    from svd_xtend_amd import build, kernels
+    from svd_xtend_amd.ops import GEGLU_TWO_PER_CU, GEMM_TILES, _dual_candidates, _tile_launched
+    lib = kernels.load_library(build.build())
+    seen, geom = set(), (ctypes.c_int * 6)()
+    dual_tiles = {v for n in (128, 160, 640) for _, v in _dual_candidates(2240, n, 64)}     # N % 160 != 0 | N % 128 != 0 | neither
+    for variant in range(41):
+        for M in (100, 560, 2240, 8960, 35840):
+            for N in (64, 128, 160, 256, 320, 640, 1280, 2560):
+                for split_k in (1, 2):
+                    for epi, aux in ((kernels.EPI_NONE, 0), (kernels.EPI_GEGLU_FWD, N // 2), (kernels.EPI_GEGLU_BWD, N)):
+                        case = (variant, M, N, split_k, epi)
+                        tile = lib.svdx_gemm_tile(variant, M, N, split_k, epi, aux, geom)
+                        assert tile == lib.svdx_gemm_tile(variant, M, N, split_k, epi, aux, None), case
+                        if variant < 2:
+                            assert tile == 0, case                          # the 64-bit-pointer kernel
+                            continue
+                        if variant >= 16 and variant not in GEMM_TILES:
+                            assert tile < 0, case                           # unknown: refused
+                            continue
+                        t = GEMM_TILES[tile]
+                        assert tuple(geom[:5]) == t[:5], (case, tile)
+                        assert bool(geom[5]) == (tile in dual_tiles), (case, tile)
+                        assert N % t.cols == 0 or t.cols == 128 or (tile in (32, 34) and epi == kernels.EPI_NONE), (case, tile)
+                        assert t.cols != 160 or epi != kernels.EPI_GEGLU_FWD, (case, tile)
+                        if epi == kernels.EPI_NONE and (variant == 4 or variant in GEMM_TILES):
+                            assert tile == _tile_launched(variant, M, N, split_k), case
+                        seen.add(tile)
+    assert seen == set(GEMM_TILES)                                          # every instantiated geometry was compared
+    assert GEMM_TILES[GEGLU_TWO_PER_CU][:5] == (192, 192, 128, 2, 8)
+    for M, N in ((35840, 2560), (2240, 1280)):                              # the GEGLU tile is launched as asked under both epilogues
+        assert lib.svdx_gemm_tile(GEGLU_TWO_PER_CU, M, N, 1, kernels.EPI_GEGLU_FWD, N // 2, None) == GEGLU_TWO_PER_CU
+        assert lib.svdx_gemm_tile(GEGLU_TWO_PER_CU, M, N, 1, kernels.EPI_GEGLU_BWD, N, None) == GEGLU_TWO_PER_CU
 
 
 def test_attention_processor_plumbing_and_forward_chunking():

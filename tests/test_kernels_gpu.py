@@ -10,7 +10,7 @@ RING = (16, 18, 20, 23, 25)  # ring-staged tile variants: between them every ins
 GROUPS = (["gemm_tn", "gemm_tn_s3", "gemm_tn_s4", "gemm_tn_v18", "gemm_geglu", "gemm_geglu_v17", "gemm_geglu_v18", "gemm_geglu_v21", "gemm_geglu_v26", "gemm_plain_v1"]
           + [f"gemm_{k}_v{v}" for v in (4, 6) + RING for k in ("plain", "gather")]
           + [f"gemm_gn_v{v}" for v in (4, 6, 8, 16, 18, 22, 23, 24, 26)]     # svdx_gemm_gn: GroupNorm statistics from the store loop of every tile family
-          + [f"gemm_{k}_v{v}" for v in (27, 28) for k in ("plain", "gather")] + ["gemm_geglu_v27"]     # tuner candidates (ops.STAGED_TILES)
+          + [f"gemm_{k}_v{v}" for v in (27, 28) for k in ("plain", "gather")] + ["gemm_geglu_v27"]     # tuner candidates (ops.GEMM_TILES rows without a rate)
           + [f"gemm_{k}_v{v}" for v in (32, 34) for k in ("plain", "gather", "gn", "geglu")]     # two-role eight-wave tiles (gemm_v5_kernel)
           + [f"gemm_{k}_v36" for k in ("plain", "gather", "gn")]     # round 6: 144 x 160 six-wave tile stepping 140 rows
           + ["large_offsets", "small", "groupnorm", "layernorm", "attention", "temporal_attention", "tsa", "encoders", "elementwise", "optim"])

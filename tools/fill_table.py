@@ -43,7 +43,7 @@ def main():
         if kind != "nt":
             continue
         s, v = ops.choose_cfg(_RT(), M, N, Kd, N, 0)
-        bm, bn, stages, waves = ops.TILE_OF_VARIANT[v]
+        bm, _, bn, stages, waves = ops.GEMM_TILES[v][:5]
         tiles = math.ceil(M / bm) * math.ceil(N / bn)
         slots = 512 if (stages == 2 and waves == 4) else 256
         wgs = tiles * s

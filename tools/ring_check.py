@@ -17,10 +17,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
 from svd_xtend_amd import kernels as K  # noqa: E402
-from svd_xtend_amd.ops import STAGED_TILES  # noqa: E402
-from svd_xtend_amd.ops import TILE_OF_VARIANT as _COST_MODEL_TILES  # noqa: E402
+from svd_xtend_amd.ops import GEGLU_TWO_PER_CU, GEMM_TILES  # noqa: E402
 
-TILE_OF_VARIANT = {**_COST_MODEL_TILES, **STAGED_TILES}      # the staged tuner candidates are screened and timed like the rest
+# (row step, columns, stages, waves); the staged tuner candidates are screened and timed like the rest
+TILE_OF_VARIANT = {v: (t.step, t.cols, t.stages, t.waves) for v, t in GEMM_TILES.items() if v != GEGLU_TWO_PER_CU}
 
 dev = torch.device("cuda")
 be = K.backend()

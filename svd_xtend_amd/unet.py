@@ -1205,13 +1205,29 @@ class UNetSpatioTemporalConditionModel(nn.Module):
         self.rt.k.rows_to_nchw(out_rows, out, g.N, self.out_channels, g.h, g.w, self.out_channels)
         return out
 
+    def _check_batch_geometry(self, B, h, w):
+        """With B > 1 the temporal blocks address their time context by `row % B` (TemporalBasicTransformerBlock._rv: diffusers' (HW, B)
+        ordering, reproduced), which is that ordering only where the level's pixel count is a multiple of B.  Refused here, before the
+        first launch, naming the level."""
+        if B == 1:
+            return
+        level = 0
+        for kind, m in self.steps:
+            if kind == "down" or kind == "up":
+                h, w = m.op.out_hw(h, w)
+                level += 1 if kind == "down" else -1
+            elif kind == "attn" and (h * w) % B:
+                raise ValueError(f"batch size {B} needs every attention level's pixel count h*w to be a multiple of {B}: level {level} "
+                                 f"is {h}x{w} = {h * w} pixels (the time context of a temporal block is taken by row % B)")
+
     def forward_rows(self, sample, timestep, ehs, added_time_ids):
         """Forward up to the channels-last prediction rows [B*T*h*w, out_channels] (activation dtype)."""
         rt = self.rt
         k = rt.k
+        B, T, Cin, h, w = sample.shape
+        self._check_batch_geometry(B, h, w)
         rt.begin_pass(0)
         self._clear_cross_pre()
-        B, T, Cin, h, w = sample.shape
         mult = 2 ** sum(1 for kind, _ in self.steps if kind == "down")
         if h % mult or w % mult:
             raise ValueError(f"latent height/width must be multiples of {mult} ({mult.bit_length() - 1} stride-2 levels; SURVEY.md 0.8)")

@@ -5,6 +5,8 @@ a hashable SIGNATURE of the launch (the host code never reads a value back from 
 it).  `run_case(backend, signature)` rebuilds seeded operands from the signature alone, launches the entry on the backend under test
 and judges every output against the float64 reference of tests/ref64.py with the error model below.  `census_cond(name)` records the
 passes around the step the same way (COND_CONFIGS: VAE encode / decode, the CLIP image path, the sampler's batch-2 forward, packing, EMA).
+`census(name)` also records the geometries beyond the two benchmarked (GEOM_EDGE, GEOM_GRID, GEOM_TINY); `geom_gpu_signatures()` is what
+the GPU runs of them: every signature of the edge geometries and one per dispatch class of the grid that nothing else reaches.
 
 Signature = (entry, ((argument name, value), ...)) in the order of `kernels.HipBackend`'s method.  A value is an int / float / bool / None,
 a `kernels.Gather`, a tuple of per-job tuples for the `*_batch` entries, or -- for a tensor -- ("T", dtype name, alias, table, n) where
@@ -22,7 +24,8 @@ Error model (derived, not measured):
   1e5 of them, mean((got - ref)/ulp) and mean((|got| - |ref|)/ulp) lie within +-0.05 (round-to-nearest: 0 +- 0.289/sqrt(n); truncation:
   -0.5 in the second; rounding toward an infinity: +-0.5 in the first).
 * multi-stage outputs: `tol_for` with the multiplier tests/kernel_checks.py uses for the family, per ROW with the row's own maximum in
-  the denominator; each stage is judged from what the launch itself stored for the previous one.
+  the denominator; each stage is judged from what the launch itself stored for the previous one.  The spatial attention backward adds
+  its cancellation term after that bar (`_attn_bwd`): D comes from the stored, rounded o.
 """
 import collections
 import contextlib
@@ -161,6 +164,56 @@ CONFIGS = {
     "c5_ref": ("svd", (1, 14, 40, 64), torch.bfloat16, 64, dict(lora_param_dtype="reference")),
     "c4": ("svd", (1, 25, 72, 128), torch.float16, 0, dict(grad_accum=2)),
 }
+# ---- geometries beyond the two benchmarked (tests/test_census_geom.py, tests/test_census_geom_gpu.py) -----------------------------------------
+# The model takes any latent height / width that are multiples of 8, any frame count and any batch size; which launches a geometry causes
+# is decided by host code (ops._choose_cfg_v4, choose_split, gn_tile_ok, fused / unfused GEGLU, tsa_fwd / tattn_fwd).
+# GEOM_EDGE: real topology, every distinct signature runs on the GPU.
+GEOM_EDGE = {
+    "e_1x1x8x8": ("svd", (1, 1, 8, 8), torch.float16, 0, {}),           # S = 64, 16, 4, 1; HW = 1; T = 1; 1x1 and 2x2 convolutions
+    "e_3x5x8x24": ("svd", (3, 5, 8, 24), torch.bfloat16, 0, {}),        # B = 3; S = 192 .. 3; row-vector groups in tsa_fwd
+    "e_1x14x24x40": ("svd", (1, 14, 24, 40), torch.float16, 0, {}),     # S = 960, 240, 60, 15: the deepest level is 3 x 5
+    "e_2x16x16x8": ("svd", (2, 16, 16, 8), torch.bfloat16, 64, {}),     # T = 16, the fused op's limit; B = 2; dual operands at small M
+    "e_1x17x16x24": ("svd", (1, 17, 16, 24), torch.float16, 0, {}),     # the first T beyond tsa_fwd
+    "e_2x14x40x64": ("svd", (2, 14, 40, 64), torch.float16, 0, {}),     # batch 2 at the benchmark geometry (run: what c2 does not launch)
+}
+GEOM_EDGE_MINUS = {"e_2x14x40x64": "c2"}          # edge geometry -> the configuration whose signatures need not run again
+
+
+def geom_refused(B, h, w, levels=4):
+    """whether the model refuses the geometry: with B > 1 every level's pixel count must be a multiple of B (unet.forward_rows)"""
+    return any(((h >> i) * (w >> i)) % B for i in range(levels))
+
+
+def _grid():
+    out = collections.OrderedDict()
+    known = {(c[1], c[2], c[3]): n for n, c in list(CONFIGS.items()) + list(GEOM_EDGE.items()) if c[0] == "svd" and not c[4]}
+    for dt, r, Ts, sizes in ((torch.float16, 0, (1, 14, 16, 17, 25), ((8, 8), (24, 40), (32, 32), (40, 64), (72, 128))),
+                             (torch.bfloat16, 64, (1, 25), ((8, 8), (24, 40), (72, 128)))):
+        for B in (1, 2):
+            for T in Ts:
+                for h, w in sizes:
+                    if geom_refused(B, h, w):
+                        continue
+                    name = known.get(((B, T, h, w), dt, r), f"g_{B}x{T}x{h}x{w}_{'lora' if r else 'full'}")
+                    out[name] = ("svd", (B, T, h, w), dt, r, {})
+    return out
+
+
+# GEOM_GRID: recorded host-only; a geometry another table already records goes under that table's name (one recording).  The grid
+# SAMPLES an unbounded domain: a geometry outside it may reach a dispatch class nothing runs.
+GEOM_GRID = _grid()
+# the tiny topology at the edge geometries it admits: the emulation and the simulator on the CPU
+GEOM_TINY = {
+    "t_1x1x8x8": ("tiny", (1, 1, 8, 8), torch.float16, 0, {}),          # 1 x 1 deepest level, S = 1, T = 1
+    "t_3x5x8x24": ("tiny", (3, 5, 8, 24), torch.bfloat16, 0, {}),       # B = 3, deepest level 1 x 3
+    "t_1x2x24x40": ("tiny", (1, 2, 24, 40), torch.float16, 0, {}),      # deepest level 3 x 5: S = 960 .. 15
+    "t_2x16x16x8": ("tiny", (2, 16, 16, 8), torch.bfloat16, 64, {}),    # T = 16, B = 2, LoRA
+    "t_1x17x8x16": ("tiny", (1, 17, 8, 16), torch.float16, 0, {}),      # the first T beyond tsa_fwd
+    "t_2x16x8x16": ("tiny", (2, 16, 8, 16), torch.float16, 0, {}),      # tsa_fwd at its limit T = 16 with the row vector grouped by B = 2
+}
+ALL_CONFIGS = dict(CONFIGS)
+for _t in (GEOM_EDGE, GEOM_GRID, GEOM_TINY):
+    ALL_CONFIGS.update(_t)
 _CACHE = {}
 
 
@@ -183,7 +236,7 @@ def census(name):
     from oracle.unet import SVD_CONFIG, TINY_CONFIG, no_default_init
     from svd_xtend_amd.train import Trainer
     from svd_xtend_amd.unet import UNetSpatioTemporalConditionModel
-    topo, (B, T, h, w), dt, lora_r, kw = CONFIGS[name]
+    topo, (B, T, h, w), dt, lora_r, kw = ALL_CONFIGS[name]
     cfg = dict(TINY_CONFIG if topo == "tiny" else SVD_CONFIG)
     rec = Recorder()
     rec.on = False
@@ -1233,7 +1286,15 @@ def run_attn_bwd_prep(be, o, a):
 def _attn_bwd(be, o, a, outs):
     """dq / dk / dv: P and dS = P (dP - D) are rounded to the activation type before the matrix unit takes them (2^-p of every term of
     the magnitude sums below), fp32 accumulation over S or 64 terms, one output rounding; lse and D come in as fp32.  Bound: the smaller
-    of that and today's bar tol_for(dt, 4) on the row's own maximum."""
+    of that and today's bar tol_for(dt, 4) on the row's own maximum -- plus the cancellation term.
+
+    Cancellation term.  D_i = sum_c o_ic dO_ic enters as the step forms it (svdx_attn_bwd_prep): from the o the forward STORED, rounded to
+    the activation type, while the float64 reference differentiates the unrounded o.  Per element |o~ - o| <= 2^-p |o| (+ half of fp16's
+    subnormal spacing), so |D~_i - D_i| <= cD_i = sum_c (2^-p |o_ic| + sub) |dO_ic|.  dS_ij = P_ij (dP_ij - D_i) moves by P_ij cD_i, and
+    the final products carry it to  dq_i: scale cD_i sum_j P_ij |k_j|,  dk_j: scale sum_i P_ij cD_i |q_i|  (dv does not read D).  No kernel
+    can do better on these operands, whatever the reference's own magnitude -- with ONE key P = 1 and dS is exactly 0 in float64, every
+    implementation returns this residue, and a bar on the row's own maximum (0) has no room for it -- so the term is added after the
+    bar's ceiling, at every S, with the rounding of the result it moves (1 + 2 * 2^-p)."""
     nb, heads, S, C = _attn_decl(o, a)
     ld, ld_o, ld_d, sc, dt = a["ld"], a["ld_o"], a["ld_d"], a["scale"], o.dtype("q")
     o.mat("d_o", nb * S, C, ld_o)
@@ -1246,8 +1307,8 @@ def _attn_bwd(be, o, a, outs):
 
     def fill_D(t):
         for b, h0, h1 in _attn_chunks(nb, heads, S):
-            ref = ref64.attention(q()[b, h0:h1], k()[b, h0:h1], v()[b, h0:h1], sc)[0]
-            t.view(nb, heads, S)[b, h0:h1] = (ref * ref64.d(do()[b, h0:h1])).sum(-1)
+            ref = ref64.attention(q()[b, h0:h1], k()[b, h0:h1], v()[b, h0:h1], sc)[0].to(dt)        # o as svdx_attn_fwd stores it
+            t.view(nb, heads, S)[b, h0:h1] = (ref64.d(ref) * ref64.d(do()[b, h0:h1])).sum(-1)
     o.decl("lse", nb * heads * S, fill_lse)
     o.decl("D", nb * heads * S, fill_D)
     for nm in outs:
@@ -1257,7 +1318,7 @@ def _attn_bwd(be, o, a, outs):
     worst, rms = {nm: (0.0, ()) for nm in outs}, {nm: RoundingMeans() for nm in outs}
     sub = 2.0 ** -25 if dt == torch.float16 else 0.0     # half of fp16's subnormal spacing: the absolute floor of one rounded P / dS term
     for b in range(nb):
-        acc = {nm: [[], []] for nm in outs}
+        acc = {nm: [[], [], []] for nm in outs}
         for _, h0, h1 in _attn_chunks(1, heads, S):
             qq, kk, vv, dd = (ref64.d(t()[b, h0:h1]) for t in (q, k, v, do))
             dq, dk, dv, _ = ref64.attention_bwd(qq, kk, vv, dd, sc)
@@ -1265,6 +1326,8 @@ def _attn_bwd(be, o, a, outs):
             Dv = (p * (dd @ vv.transpose(-1, -2))).sum(-1, keepdim=True)
             ads = p * (dd.abs() @ vv.abs().transpose(-1, -2) + Dv.abs())
             one = torch.ones(h1 - h0, S, 1, dtype=torch.float64, device=o.dev)
+            cD = ((_UA[dt] * (p @ vv).abs() + sub) * dd.abs()).sum(-1, keepdim=True) * (1 + 2 * _UA[dt])
+            canc = dict(dq=sc * cD * (p @ kk.abs()), dk=sc * ((p * cD).transpose(-1, -2) @ qq.abs()), dv=None)
             mags = dict(dq=(dq, sc * (ads @ kk.abs()), sc * kk.abs().sum(1, keepdim=True) * one), dk=(dk, sc * (ads.transpose(-1, -2) @ qq.abs()), sc * qq.abs().sum(1, keepdim=True) * one),
                         dv=(dv, p.transpose(-1, -2) @ dd.abs(), dd.abs().sum(1, keepdim=True) * one))
             for nm in outs:
@@ -1272,12 +1335,13 @@ def _attn_bwd(be, o, a, outs):
                 r = 2 if nm == "dv" else 3
                 acc[nm][0].append(ref)
                 acc[nm][1].append((r * _UA[dt] + (S + 3 * 64 + 8) * 2.0 ** -23) * Sm + sub * fl)
-            del p, ads
+                acc[nm][2].append(torch.zeros_like(ref) if canc[nm] is None else canc[nm])
+            del p, ads, canc
         for nm in outs:
-            ref, derived = torch.cat(acc[nm][0], 0), torch.cat(acc[nm][1], 0)
+            ref, derived, cterm = (torch.cat(x, 0) for x in acc[nm])
             r = 2 if nm == "dv" else 3
             bar = tol_for(dt, 4) * ref.abs().amax((0, 2), keepdim=True).expand_as(ref)          # a row holds all heads
-            bound = torch.maximum(torch.minimum(bar, derived + _half_ulp_after(ref, r * _UA[dt], dt)), 0.5 * ulp_of(ref, dt))
+            bound = torch.maximum(torch.minimum(bar, derived + _half_ulp_after(ref, r * _UA[dt], dt)) + cterm, 0.5 * ulp_of(ref, dt))
             w = _worst(_ratio(_hv(o[nm], nb, S, heads, ld_d)[b], ref, bound))
             worst[nm] = max(worst[nm], (w[0], (b,) + w[1]))
             rms[nm].add(_hv(o[nm], nb, S, heads, ld_d)[b], ref, dt)
@@ -1905,6 +1969,48 @@ def run_geglu_fwd(be, o, a):
     return res
 
 
+@runner("geglu_bwd")
+def run_geglu_bwd(be, o, a):
+    """the unfused form (the step launches it where the fused epilogue does not apply): dpre = [dout gelu(g), dout a gelu'(g)] from a
+    16-bit dout -- the factor in fp32 (its error absolute: a few 2^-23 of |g| / |a| (1 + |g|), as in the GEMM's GEGLU-backward epilogue),
+    one product, one rounding.  Ceiling: that family's bar, tol_for(dt, 2) on the row's own maximum."""
+    M, Fd = a["M"], a["F"]
+    o.mat("dout", M, Fd)
+    o.mat("pre", M, 2 * Fd)
+    o.out("dpre", M, 2 * Fd)
+    o.alloc()
+    _launch(be, o)
+    dt = o.dtype("pre")
+    pre, dh = _v(o["pre"], M, 2 * Fd, 2 * Fd), ref64.d(_v(o["dout"], M, Fd, Fd))
+    ref = ref64.geglu_bwd(dh, pre, Fd)
+    p64 = ref64.d(pre)
+    facmag = torch.cat([p64[:, Fd:].abs(), p64[:, :Fd].abs() * (1 + p64[:, Fd:].abs())], 1)
+    derived = 0.5 * ulp_of(ref, dt) + 2.0 ** -24 * ref.abs() + 16 * 2.0 ** -23 * torch.cat([dh, dh], 1).abs() * facmag
+    res = []
+    judge_rows(res, "dpre", _v(o["dpre"], M, 2 * Fd, 2 * Fd), ref, tol_for(dt, 2), derived)
+    return res
+
+
+@runner("colsum")
+def run_colsum(be, o, a):
+    """out[g, c] (+)= the sum of x[r, c] over the rows of group g, in fp32: single-rounding bound with as many accumulated terms as the
+    largest group has rows (through the scratch slabs or atomics, in any order), + 1 for the value it adds to"""
+    rows, C, ldx, ng, rpg, mod, accf = a["rows"], a["C"], a["ldx"], a["n_groups"], a["rpg"], a["mod"], int(a["accumulate"])
+    o.mat("x", rows, C, ldx)
+    o.out("out", ng, C, fill=1.0 if accf else float("nan"))
+    o.out("scratch", 1, K.colsum_slabs(rows, rpg, mod) * ng * C)
+    o.alloc()
+    _launch(be, o)
+    x = ref64.d(_v(o["x"], rows, C, ldx))
+    gi = ref64.group_index(rows, rpg, mod, o.dev)
+    assert int(gi.max()) < ng, (rows, rpg, mod, ng)
+    base = torch.full((ng, C), float(accf), dtype=torch.float64, device=o.dev)
+    v, S = base.clone().index_add_(0, gi, x), base.clone().index_add_(0, gi, x.abs())
+    res = []
+    judge_single(res, "out", _v(o["out"], ng, C, C), v, S, int(torch.bincount(gi).max()), 1 + accf)
+    return res
+
+
 @runner("softmax_rows")
 def run_softmax_rows(be, o, a):
     """p = exp2(x sl2 - max sl2) / sum, sl2 = scale log2(e) as a float.  Rounding points: the input (given) and the output; fp32 between.
@@ -2055,6 +2161,42 @@ def cond_gpu_signatures(what):
         rest = collections.Counter({s: n for s, n in real.items() if dispatch_class(s) not in reached})
         if rest:
             parts[COND_REAL[what]] = rest
+    return parts
+
+
+STEP_GPU = ("c2", "c2_clip", "c5", "c5_ref", "c4")          # what tests/test_census_gpu.py runs
+
+
+def sig_rows(sig):
+    """the row count of a launch: what the geometry scales (0 for the entries that have none)"""
+    a = sig_args(sig)
+    for keys in (("M",), ("R",), ("n_s", "rows"), ("rows",), ("nb", "S"), ("B", "T", "HW"), ("n_img", "h", "w"), ("n",)):
+        if all(isinstance(a.get(k), int) for k in keys):
+            return math.prod(a[k] for k in keys)
+    return 0
+
+
+def geom_gpu_signatures():
+    """{part name: Counter[signature]} of what tests/test_census_geom_gpu.py runs: every signature of the GEOM_EDGE geometries (less
+    what GEOM_EDGE_MINUS says runs already) and, as part "grid", one signature for every dispatch class of GEOM_GRID that neither those
+    nor the step's own configurations (STEP_GPU) reach: the one with the fewest rows -- a class only large row counts reach runs there."""
+    if "geom_gpu" in _CACHE:
+        return _CACHE["geom_gpu"]
+    parts = collections.OrderedDict()
+    for n in GEOM_EDGE:
+        skip = census(GEOM_EDGE_MINUS[n]) if n in GEOM_EDGE_MINUS else ()
+        parts[n] = collections.Counter({s: k for s, k in census(n).items() if s not in skip})
+    reached = {dispatch_class(s) for c in parts.values() for s in c} | {dispatch_class(s) for n in STEP_GPU for s in census(n)}
+    best = {}
+    for n in GEOM_GRID:
+        for s, k in census(n).items():
+            cls = dispatch_class(s)
+            if cls not in reached:
+                key = (sig_rows(s), repr(s))
+                if cls not in best or key < best[cls][0]:
+                    best[cls] = (key, s)
+    parts["grid"] = collections.Counter({s: 1 for _, s in best.values()})
+    _CACHE["geom_gpu"] = parts
     return parts
 
 

@@ -47,9 +47,10 @@ import emul  # noqa: E402  (the FORMAT of the fixed-point GroupNorm statistics b
 import ref64  # noqa: E402
 from kernel_checks import tol_for  # noqa: E402  (the project's bar for the multi-stage families)
 
-# entries that compute nothing numeric: the host-side state machine of the loss scale, the finite flag, launch plans, clocks.  (The memsets
-# `zero` / `zero_spans` have runners: the bytes are zero and nothing beside them is touched.)
-ALLOW_LIST = ("optim_prep", "check_finite", "check_finite_spans", "plan_begin", "plan_end", "stamp")
+# entries that launch nothing of their own: launch plans, clocks.  (The memsets `zero` / `zero_spans` have runners: the bytes are zero and
+# nothing beside them is touched; so have the finite checks -- the flag stays down on finite floats and one planted value raises it -- and
+# the loss-scale state machine `optim_prep`, against the float64 restatement of tests/overflow_checks.py.)
+ALLOW_LIST = ("plan_begin", "plan_end", "stamp")
 ALLOW_FRACTION = 0.02
 
 _PARAMS = {n: list(inspect.signature(f).parameters.values())[1:] for n, f in inspect.getmembers(K.HipBackend, inspect.isfunction)
@@ -1782,6 +1783,75 @@ def run_zero_spans(be, o, a):
     bits = o["base"].view(torch.int32)
     return [("spans: all bytes zero", 0.0 if bool((bits[inside] == 0).all()) else float("inf"), ()),
             ("outside the spans untouched", 0.0 if bool((o["base"][~inside] == 1.0).all()) else float("inf"), ())]
+
+
+# ---- the inf check and the loss-scale state machine ------------------------------------------------------------------------------------------
+STATE_FILL = 7.0           # what the state floats a finite check must not touch are pre-filled with
+NON_FINITE = (float("inf"), float("-inf"), float("nan"))
+
+
+def _finite_check(be, o, g_name, n, place, overrides=None):
+    """a finite buffer leaves opt_state[3] at 0; one non-finite float at `place` raises it; the rest of the state is never written"""
+    o.vec(g_name, n)
+    o.decl("opt_state", K.OPT_STATE_ALLOC, lambda t: t.fill_(STATE_FILL), out=True)
+    o.alloc()
+    want = torch.full((K.OPT_STATE_ALLOC,), STATE_FILL, device=o.dev)
+    res = []
+    for planted in (False, True):
+        o["opt_state"][3] = 0.0
+        want[3] = 1.0 if planted else 0.0
+        if planted:
+            o[g_name][place] = NON_FINITE[sig_seed(o.sig) % 3]
+        _launch(be, o, overrides() if overrides else None)
+        judge_exact(res, f"found_inf raised by the float at {place}" if planted else "found_inf stays 0", o["opt_state"], want)
+    return res
+
+
+@runner("check_finite_spans")
+def run_check_finite_spans(be, o, a):
+    """the recorded span table; the planted float is element (seed / n_spans) mod count of span seed mod n_spans"""
+    spans = o.table("spans").view(-1, 2)[:a["n_spans"]]
+    off, cnt = spans[sig_seed(o.sig) % len(spans)].tolist()
+    return _finite_check(be, o, "g", int((spans[:, 0] + spans[:, 1]).max()), off + (sig_seed(o.sig) // len(spans)) % cnt,
+                         lambda: dict(spans=o["spans"].view(-1, 2)))
+
+
+@runner("check_finite")
+def run_check_finite(be, o, a):
+    """the recorded n; the planted float is element seed mod n"""
+    return _finite_check(be, o, "g", a["n"], sig_seed(o.sig) % a["n"])
+
+
+@runner("optim_prep")
+def run_optim_prep(be, o, a):
+    """the recorded arguments from step 3 at scale 1024 (1 when static), found and not found, the growth tracker at 0 and one short of the
+    interval: step, scale, tracker, the cleared flag, 1 / scale and the skip flag exact, the bias corrections and the schedule multiplier at
+    tests/kernel_checks.check_optim's bars, against the float64 restatement of GradScaler's rule (tests/overflow_checks.grad_scaler_rule)"""
+    import overflow_checks as oc
+    from kernel_checks import relerr
+    o.decl("opt_state", K.OPT_STATE_ALLOC, lambda t: t.zero_(), out=True)
+    o.alloc()
+    interval, dynamic = a["growth_interval"], a["dynamic"]
+    b1, b2 = (float(torch.tensor(b, dtype=torch.float32)) for b in (a["beta1"], a["beta2"]))
+    res = []
+    for found in (False, True):
+        for tracker in sorted({0.0, float(max(interval - 1, 0))}):
+            scale = 1024.0 if dynamic else 1.0
+            st = [3.0, scale, tracker, 1.0 if found else 0.0, STATE_FILL, STATE_FILL, STATE_FILL, STATE_FILL, STATE_FILL] + [0.0] * 7
+            st += [STATE_FILL] * (K.OPT_STATE_ALLOC - len(st))
+            o["opt_state"].copy_(torch.tensor(st))
+            _launch(be, o)
+            got = o["opt_state"].cpu()
+            s1, t1 = oc.grad_scaler_rule(scale, tracker, found, interval, dynamic, a["growth"], a["backoff"])
+            step = 3.0 if found else 4.0
+            label = f"found={found} tracker={tracker:g}: "
+            judge_exact(res, label + "step, scale, tracker, found_inf, 1 / scale", got[:5], torch.tensor([step, s1, t1, 0.0, 1.0 / scale], dtype=torch.float32))
+            judge_exact(res, label + "skip", got[7:8], torch.tensor([1.0 if found else 0.0]))
+            bc = torch.tensor([1.0 - b1 ** step, 1.0 - b2 ** step], dtype=torch.float64)
+            res.append((label + "bias corrections", relerr(got[5:7], bc) / 1e-5, ()))
+            res.append((label + "lr multiplier (constant schedule)", abs(float(got[8]) - 1.0) / 5e-6, ()))
+            judge_exact(res, label + "schedule and rule floats untouched", got[9:], torch.tensor(st[9:]))
+    return res
 
 
 # ---- the conditioners' own kernels (csrc/encoders.hip) and the layout passes --------------------------------------------------------------

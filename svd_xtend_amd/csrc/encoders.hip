@@ -1,6 +1,6 @@
 // encoders.hip -- the few kernels the frozen conditioners either side of the UNet step need beyond the UNet's own set
 // (SURVEY.md 8f ranks 1-2): the VAE encoder of `tensor_to_vae_latent` (/root/reference/train_svd.py:283-291) and the CLIP image
-// tower of `encode_image` (:857-876).  Their convolutions, linears, GroupNorm / LayerNorm run on the kernels of gemm.hip / norm.hip;
+// tower of `encode_image` (:857-876).  Their convolutions, linears, GroupNorm / LayerNorm run on the kernels of gemm_nt.hip / norm.hip;
 // here are
 //   * patch_rows     -- im2col of a FEW-channel image (cin = 3) into GEMM rows: the VAE's conv_in (3x3, pad 1) and CLIP's patch
 //                       embedding (14x14, stride 14).  K = cin*kh*kw is zero-padded to the GEMM's K granule; 27 -> 64 costs 2.4x the

@@ -272,9 +272,9 @@ class Tile(NamedTuple):
     #                            per CU for it.  None: not in the cost model
 
 
-GEGLU_TWO_PER_CU = 26      # 192 x 128, eight waves, two stages: 80 KB of LDS, two workgroups per CU (csrc/gemm.hip); used under GEGLU epilogues only
+GEGLU_TWO_PER_CU = 26      # 192 x 128, eight waves, two stages: 80 KB of LDS, two workgroups per CU (csrc/gemm_nt.hip); used under GEGLU epilogues only
 
-# Rows with a rate are what the cost model (choose_cfg) searches.  Rows without one are instantiated in csrc/gemm.hip and offered to the
+# Rows with a rate are what the cost model (choose_cfg) searches.  Rows without one are instantiated in csrc/gemm_nt.hip and offered to the
 # in-situ tuner (bench.py --tune) only -- except GEGLU_TWO_PER_CU, which geglu_candidates adds under the fused epilogues:
 #   27 / 28: two-stage eight-wave tiles without a measured rate;
 #   32 / 34: round 6's two-role eight-wave tiles (gemm_v5_kernel: 256 x 256 and 160 x 320).  Isolated they are the fastest kernels of the library
@@ -304,7 +304,7 @@ _ALONE, _FILL_STEPS, _EPI_US, _FIN_US, _FIN_BYTES_PER_US = 0.5, 1.5, 3.0, 12.0, 
 
 
 def _xcd_block_tiles(Tm: int, Tn: int, a_bytes: float, b_bytes: float) -> int:
-    """Tiles owned by the fullest XCD under launch_gemm_v4's arrangement of the 8 XCDs over the tile grid (csrc/gemm.hip).  (With 2 / 4 / 8
+    """Tiles owned by the fullest XCD under launch_gemm_v4's arrangement of the 8 XCDs over the tile grid (csrc/gemm_nt.hip).  (With 2 / 4 / 8
     K slices the launcher may give every slice XCDs of its own -- `z_xcd`, round 4 -- which fills no worse by construction; the model
     keeps the slice-agnostic count its rates were fitted with.)"""
     best_eff, best = 0.0, None
@@ -489,7 +489,7 @@ def tuned_call(rt: "Runtime", key, make_cands, fallback, run) -> None:
 
 def gn_tile_ok(variant: int, N: int, rows: int, cg: int) -> bool:
     """Can the tile `variant` take GroupNorm statistics in its store loop (svdx_gemm_gn)?  Whole column tiles, and a tile that touches
-    at most 8 samples and 36 groups (csrc/gemm.hip: GN_MAX_S / GN_MAX_G)."""
+    at most 8 samples and 36 groups (csrc/gemm_nt.hip: GN_MAX_S / GN_MAX_G)."""
     t = GEMM_TILES.get(variant)
     if t is None or variant == GEGLU_TWO_PER_CU:             # (the GEGLU tile is no candidate of gemm_act)
         return False
@@ -511,7 +511,7 @@ def gemm_act(rt: "Runtime", A, B, out, M, N, Kd, lda, ldb, ldc, bias=None, rowve
     splittable = rt.split_k and N % 4 == 0 and ldc % 4 == 0
     key = ("nt", M, N, Kd, lda, ldc, 0 if gather is None else (gather.mode, gather.stride, gather.ups, gather.cin),
            bias is not None, rowvec is not None, res is not None, gn is not None) + (() if dual is None else (("dual", dual[2]),))
-    # svdx_gemm_gn serves operands below 2 GiB only (buffer descriptors; csrc/gemm.hip returns -2 beyond that): larger operands keep the
+    # svdx_gemm_gn serves operands below 2 GiB only (buffer descriptors; csrc/gemm_nt.hip returns -2 beyond that): larger operands keep the
     # separate statistics pass instead of turning a working forward into an error
     gn_fits = gn is not None and max(A.numel() * A.element_size(), B.numel() * B.element_size()) < (1 << 31)
     assert alpha == 1.0 or dual is None
@@ -675,7 +675,7 @@ class LinearOp:
 
 # Round 4 timed eight-wave 128 x 256 / 128 x 384 / 256 x 128 weight-gradient tiles (two and three stages) inside the step: the four-wave
 # 128 x 128 tile with two workgroups per CU won every problem by 5-40 % (profiles/r4_dropped_experiments.txt, item 2); they were removed again.
-# Round 5: with the staging hidden from the compiler's wait pass (csrc/gemm.hip hidden_dma) loads and MFMAs overlap for the first time, so the
+# Round 5: with the staging hidden from the compiler's wait pass (csrc/gemm_tn.hip hidden_dma) loads and MFMAs overlap for the first time, so the
 # deeper rings of the 128 x 128 tile (stages 3 / 4: one workgroup per CU, 2 / 3 tiles in flight) are offered to the in-situ tuner again.
 STAGED_TN_TILES = {3: (128, 128), 4: (128, 128)}
 
@@ -705,7 +705,7 @@ def _tn_formula(M: int, N: int, Kd: int):
 
 
 def _tn_slices(sk: int) -> int:
-    """Row-slice counts the TN kernels place well on the 8 XCDs (csrc/gemm.hip tn_who): 1, 2, 4 (a slice owns 8 / sk XCDs) or a multiple of 8
+    """Row-slice counts the TN kernels place well on the 8 XCDs (csrc/gemm_tn.hip tn_who): 1, 2, 4 (a slice owns 8 / sk XCDs) or a multiple of 8
     (an XCD owns whole slices); the largest such count <= sk."""
     return sk // 8 * 8 if sk >= 8 else (4 if sk >= 4 else 2 if sk >= 2 else 1)
 

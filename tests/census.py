@@ -664,7 +664,7 @@ def _gather_src_rows(g):
 
 
 def coalesced_columns(a, C, res):
-    """Leading columns of an activation-output GEMM that leave through csrc/gemm.hip's LDS-parked, coalesced stores (gemm_v4_kernel,
+    """Leading columns of an activation-output GEMM that leave through csrc/gemm_nt.hip's LDS-parked, coalesced stores (gemm_v4_kernel,
     epilogue A): the launch resolves to one of the four-/eight-wave tiles, C and the residual are 16-byte aligned with pitches that
     are multiples of 8, and the column tile is whole (n0 + BN <= N: a partial last tile takes the direct epilogue).  Every other
     element gets the residual in fp32 before its one rounding."""
@@ -776,7 +776,7 @@ def run_gemm(be, o, a):
     C = _v(o["C"], M, N, a["ldc"])
     extra = None
     if kw["res"] is not None and mode == K.OUT_ACT:
-        # csrc/gemm.hip, coalesced-store epilogue of the 128-row tiles: alpha A B^T + bias + row vector is rounded to the activation type,
+        # csrc/gemm_nt.hip, coalesced-store epilogue of the 128-row tiles: alpha A B^T + bias + row vector is rounded to the activation type,
         # parked in LDS, and the residual is added to THAT on the way out -- a second rounding point, at the magnitude of the value before
         # the residual (the reference model's `conv(x)` then `+ residual` in 16-bit autocast has the same two).  Granted to the columns
         # that take that path only.  profiles/census_gpu.txt

@@ -21,7 +21,7 @@ CSRC = os.environ.get("SVDX_SIM_CSRC") or os.path.join(ROOT, "svd_xtend_amd", "c
 OUT = os.environ.get("SVDX_SIM_OUT") or os.path.join(HERE, "_build")
 LIB = os.path.join(OUT, "libsvdx_sim.so")
 CXX = os.environ.get("SVDX_SIM_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-OPT = os.environ.get("SVDX_SIM_OPT", "-O0")      # kernel sources: -O0 compiles gemm.hip's instantiations in seconds (-O1: most of a minute); the scheduler is -O2
+OPT = os.environ.get("SVDX_SIM_OPT", "-O0")      # kernel sources: -O0 compiles gemm_nt.hip's instantiations in seconds (-O1: most of a minute); the scheduler is -O2
 FLAGS = ["-std=c++17", "-fPIC", "-pthread", "-Wno-unused-value", "-Wno-pass-failed", "-Wno-unknown-pragmas", "-Wno-deprecated-declarations",
          "-ffp-contract=off", "-I", HERE]
 

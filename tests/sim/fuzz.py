@@ -115,7 +115,7 @@ def fuzz_tn(P, dt, rng, g):
     sk = 1
     if mode == K.OUT_F32_SLAB:
         kt = (R + 63) // 64
-        sk = rng.choice([x for x in (1, 2, 3, 4, 8, 16, 24) if x <= kt] or [1])       # incl. the slice counts ops._tn_slices asks for (XCD maps of csrc/gemm.hip tn_who)
+        sk = rng.choice([x for x in (1, 2, 3, 4, 8, 16, 24) if x <= kt] or [1])       # incl. the slice counts ops._tn_slices asks for (XCD maps of csrc/gemm_tn.hip tn_who)
         while sk > 1 and (kt + sk - 1) // sk * (sk - 1) >= kt:
             sk -= 1
         outs = dict(C=torch.full((sk, N, Kd), float("nan"), device=P.dev), cs=torch.full((sk, N), 7.0, device=P.dev))      # every slab element has exactly one writer

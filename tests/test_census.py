@@ -53,7 +53,7 @@ def test_every_census_entry_has_a_runner_or_is_allow_listed(name):
 
 def test_no_c4_operand_reaches_the_64_bit_pointer_kernel():
     """svdx_gemm takes its 64-bit-pointer kernel (and refuses fused epilogues) when the extent of A or B reaches 2 GiB: the extents as
-    csrc/gemm.hip's entry computes them -- A over the gather's source rows with the gather's pitch, B = (N - 1) ldb + K -- from the
+    csrc/gemm_nt.hip's entry computes them -- A over the gather's source rows with the gather's pitch, B = (N - 1) ldb + K -- from the
     signatures of config 4.  (Every signature runs on the GPU whichever kernel it takes; this says which.)"""
     worst = 0
     for s in census.census("c4"):

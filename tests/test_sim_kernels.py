@@ -160,12 +160,14 @@ MUTATIONS = {
     # a counted wait that leaves one tile too many in flight: the ring's next stage is read before its LDS-DMA has landed
     "lax_vmcnt": ('if (t == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPIECE) : "memory");',
                   'if (t == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NPIECE) : "memory");', "gemm_plain_v16"),
-    # no workgroup barrier between the K-steps of the ring: a fast wave overwrites the stage a slow wave still reads
+    # no workgroup barrier between the K-steps of the ring: a fast wave overwrites the stage a slow wave still reads.  The barrier is shared
+    # code (gemm_common.h: stage_barrier), so it is taken from an NT tile with a counted ring and from a TN group with one
     "no_barrier": ("__builtin_amdgcn_s_barrier();", "/* removed */", "gemm_plain_v16"),
+    "no_barrier_tn": ("__builtin_amdgcn_s_barrier();", "/* removed */", "gemm_tn_s3"),
 }
 
 
-@pytest.mark.skipif(not FULL, reason="SVDX_SIM_FULL=1: rebuilds the simulator library from a mutated copy of gemm.hip (about a minute each)")
+@pytest.mark.skipif(not FULL, reason="SVDX_SIM_FULL=1: rebuilds the simulator library from a mutated copy of the GEMM sources (about a minute each)")
 @pytest.mark.parametrize("name", sorted(MUTATIONS))
 def test_simulator_notices_mutation(tmp_path, name):
     import subprocess
@@ -176,9 +178,10 @@ def test_simulator_notices_mutation(tmp_path, name):
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".h", ".cpp")):
             shutil.copy(os.path.join(csrc, f), mut / f)
-    src = (mut / "gemm.hip").read_text()
-    assert old in src
-    (mut / "gemm.hip").write_text(src.replace(old, new))
+    hit = [f for f in sorted(mut.glob("gemm*")) if old in f.read_text()]        # the ring's waits are the kernels' (gemm_nt.hip), its barrier is gemm_common.h's
+    assert hit
+    for f in hit:
+        f.write_text(f.read_text().replace(old, new))
     env = dict(os.environ, SVDX_SIM_CSRC=str(mut), SVDX_SIM_OUT=str(tmp_path / "out"))
     r = subprocess.run([sys.executable, os.path.join(HERE, "sim", "run_checks.py"), group, "--f16"], env=env, capture_output=True, text=True)
     assert r.returncode == 1 and " bad " in r.stdout and "  0 bad" not in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -1,6 +1,6 @@
 // Register-stationary weights for the short-K projections of the 64x40 level (round-4 probe for round 5).
 //   C[M, N] = A[M, K] W[N, K]^T, fp16, K = 320, N a multiple of 320 (320: the square projections; 960: q/k/v; 2560: the feed-forward's first linear)
-// The production tiles (csrc/gemm.hip) stage both operands through LDS and run 448 workgroups in lock-step: a 35840 x 320 x 320
+// The production tiles (csrc/gemm_nt.hip) stage both operands through LDS and run 448 workgroups in lock-step: a 35840 x 320 x 320
 // projection takes 18.5 us where its 46 MB are 8 us of HBM time.  Here a wave keeps ITS 80 columns of W (5 column tiles x 10 K-steps
 // = 50 fragments = 200 registers) in registers for the whole launch and streams 16-row tiles of A straight from global memory into
 // MFMA operands: no LDS, no barrier, loads of row tile i + 1 under the 50 MFMAs of tile i, results leave as 8-byte stores.

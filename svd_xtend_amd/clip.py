@@ -17,7 +17,6 @@ SURVEY.md 8(f) rank 2.  The tower is frozen (:660) and runs once per clip on its
 Forward only."""
 from __future__ import annotations
 
-import json
 import os
 from types import SimpleNamespace
 from typing import Optional, Sequence
@@ -26,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from .ops import LayerNormOp, LinearOp, Runtime, gemm_act, rup
-from .unet import FrozenConfig
+from .pretrained import FrozenConfig, PretrainedMixin
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)        # CLIPImageProcessor defaults (train_svd.py:640-641, :864-871)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -89,8 +88,12 @@ class _VisionTransformer(nn.Module):
         self.post_layernorm = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
 
 
-class CLIPVisionModelWithProjection(nn.Module):
-    """Config fields of transformers.CLIPVisionConfig; defaults = the SVD `image_encoder` (OpenCLIP ViT-H/14)."""
+class CLIPVisionModelWithProjection(PretrainedMixin, nn.Module):
+    """Config fields of transformers.CLIPVisionConfig; defaults = the SVD `image_encoder` (OpenCLIP ViT-H/14).  `from_pretrained`:
+    `<path>/<subfolder>/config.json` + `model[.<variant>].safetensors` (train_svd.py:646-648)."""
+
+    weights_name = "model{variant}.safetensors"
+    skip_keys = ("vision_model.embeddings.position_ids",)
 
     def __init__(self, hidden_size: int = 1280, intermediate_size: int = 5120, projection_dim: int = 1024, num_hidden_layers: int = 32,
                  num_attention_heads: int = 16, num_channels: int = 3, image_size: int = 224, patch_size: int = 14,
@@ -107,33 +110,19 @@ class CLIPVisionModelWithProjection(nn.Module):
         self.vision_model = _VisionTransformer(self.config)
         self.visual_projection = nn.Linear(hidden_size, projection_dim, bias=False)
         self.rt: Optional[Runtime] = None
-        self._requested_dtype = None
 
     @classmethod
-    def from_pretrained(cls, path, subfolder: Optional[str] = None, variant: Optional[str] = None, torch_dtype=None, **unused):
-        """`<path>/<subfolder>/config.json` + `model[.<variant>].safetensors` (train_svd.py:646-648)."""
-        from safetensors.torch import load_file
-        folder = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(folder, "config.json")) as f:
-            raw = json.load(f)
-        cfg = {k: v for k, v in {**raw.get("vision_config", {}), **raw}.items() if not k.startswith("_") and k not in ("vision_config", "text_config")}
-        model = cls(**cfg)
-        names = [f"model.{variant}.safetensors"] if variant else []
-        wpath = next((os.path.join(folder, n) for n in names + ["model.safetensors"] if os.path.exists(os.path.join(folder, n))), None)
-        if wpath is None:
-            raise FileNotFoundError(f"no model[.{variant}].safetensors under {folder}")
-        sd = {k: v.float() for k, v in load_file(wpath).items() if k != "vision_model.embeddings.position_ids"}
-        model.load_state_dict(sd, strict=True)
-        if torch_dtype is not None and torch_dtype != torch.float32:
-            model._requested_dtype = torch_dtype
-        return model
+    def _config_args(cls, raw):
+        """a whole-CLIP config keeps the tower's fields under `vision_config`; top-level fields win"""
+        flat = {**raw.get("vision_config", {}), **raw}
+        return {k: v for k, v in super()._config_args(flat).items() if k not in ("vision_config", "text_config")}
 
-    def to(self, *args, **kwargs):
-        device, dtype, non_blocking, _ = torch._C._nn._parse_to(*args, **kwargs)
-        if dtype is not None and dtype.is_floating_point and dtype != torch.float32:
-            self._requested_dtype = dtype
-            return super().to(device=device, non_blocking=non_blocking) if device is not None else self
-        return super().to(*args, **kwargs)
+    @classmethod
+    def _weights_file(cls, folder, variant):
+        wpath = super()._weights_file(folder, variant)
+        if not os.path.exists(wpath):
+            raise FileNotFoundError(f"no model[.{variant}].safetensors under {folder}")
+        return wpath
 
     def prepare(self, dtype: Optional[torch.dtype] = None) -> "CLIPVisionModelWithProjection":
         dtype = dtype or self._requested_dtype or torch.float16

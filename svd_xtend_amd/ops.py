@@ -12,6 +12,7 @@ from __future__ import annotations
 import contextlib
 import functools
 import os
+from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import List, NamedTuple, Optional, Sequence
 
@@ -497,42 +498,42 @@ def gn_tile_ok(variant: int, N: int, rows: int, cg: int) -> bool:
 
 
 def gemm_act(rt: "Runtime", A, B, out, M, N, Kd, lda, ldb, ldc, bias=None, rowvec=None, rv_ld=0, rv_rpg=0, rv_mod=0,
-             res=None, ldres=0, gather=None, dual=None, alpha: float = 1.0, gn=None) -> bool:
+             res=None, ldres=0, gather=None, dual=None, alpha: float = 1.0, gn: Optional[GnStats] = None) -> None:
     """Activation-dtype GEMM.  Tile shape and split-K factor come from the GemmTuner table when the model was tuned
     (Trainer.tune_gemms), else from a formula: the 10x16 / 5x8 latent levels (M = 2240 / 560 rows against K up to 23040)
     cannot fill 256 CUs with output tiles alone, so the reduction is split across blocks -- partial sums go to float slabs
     that a small epilogue kernel reduces, applying bias/row-vector/residual.
     dual = (A2, B2, K2, lda2, ldb2): out also gets A2 B2^T (the LoRA term) -- inside the same launch when the reduction is not
     split, by a second accumulate launch when it is.
-    gn = (stats, rows, cg): the GroupNorm that consumes `out` wants its statistics (zeroed opaque buffer of svdx_gn_stats; sample =
-    `rows` consecutive rows, group = `cg` consecutive channels).  Returns True when the launch left them there (unsplit launch of a
-    tile whose store loop can take them); False: the caller runs svdx_gn_stats as before."""
+    gn (GnStats, from GroupNormOp.want): the GroupNorm that consumes `out` wants its statistics.  `gn.filled` is set when the launch
+    left them there (unsplit launch of a tile whose store loop can take them, or the reducing launch of a split one); otherwise the
+    norm runs svdx_gn_stats as before.  The backend takes the plain (stats, rows, cg)."""
     k = rt.k
     splittable = rt.split_k and N % 4 == 0 and ldc % 4 == 0
     key = ("nt", M, N, Kd, lda, ldc, 0 if gather is None else (gather.mode, gather.stride, gather.ups, gather.cin),
            bias is not None, rowvec is not None, res is not None, gn is not None) + (() if dual is None else (("dual", dual[2]),))
     # svdx_gemm_gn serves operands below 2 GiB only (buffer descriptors; csrc/gemm_nt.hip returns -2 beyond that): larger operands keep the
     # separate statistics pass instead of turning a working forward into an error
-    gn_fits = gn is not None and max(A.numel() * A.element_size(), B.numel() * B.element_size()) < (1 << 31)
+    gn_fits = max(A.numel() * A.element_size(), B.numel() * B.element_size()) < (1 << 31)
     assert alpha == 1.0 or dual is None
-
-    done = [False]
+    assert gn is None or not gn.filled, "a statistics handle belongs to one tensor: one producing launch"
+    ask = gn is not None and dual is None and rt.fuse_gn_stats          # (an unfused adapter term would change `out` after its statistics)
 
     def run(cfg):
         split, variant = cfg
         fused = dual if (split == 1 and rt.fuse_dual) else None
+        take = None
         if split == 1:
-            take = gn if (gn_fits and dual is None and rt.fuse_gn_stats and ldc % 8 == 0 and gn_tile_ok(_tile_launched(variant, M, N), N, gn[1], gn[2])) else None
-            done[0] = take is not None
+            if ask and gn_fits and ldc % 8 == 0 and gn_tile_ok(_tile_launched(variant, M, N), N, gn.rows, gn.cg):
+                take, gn.filled = (gn.stats, gn.rows, gn.cg), True
             k.gemm(A, B, out, M, N, Kd, lda, ldb, ldc, bias=bias, rowvec=rowvec, rv_ld=rv_ld, rv_rpg=rv_rpg, rv_mod=rv_mod,
                    res=res, ldres=ldres, gather=gather, variant=variant, dual=fused, alpha=alpha, gn=take)
         else:
             acc = rt.f32(split, M, N)
             k.gemm(A, B, acc, M, N, Kd, lda, ldb, N, gather=gather, out_mode=K.OUT_F32_SLAB, split_k=split, variant=variant, alpha=alpha)
             # the reducing launch writes the tensor: the statistics ride there (a block's 1024 consecutive elements: <= 2 samples)
-            # (dual is None: an unfused adapter term below would change `out` after its statistics were taken)
-            take = gn if (gn is not None and dual is None and rt.fuse_gn_stats and N * gn[1] >= 1024 and N // gn[2] <= 64) else None
-            done[0] = take is not None
+            if ask and N * gn.rows >= 1024 and N // gn.cg <= 64:
+                take, gn.filled = (gn.stats, gn.rows, gn.cg), True
             k.gemm_finalize(acc, split, M * N, out, M, N, ldc, bias=bias, rowvec=rowvec, rv_ld=rv_ld, rv_rpg=rv_rpg,
                             rv_mod=rv_mod, res=res, ldres=ldres, gn=take)
         if dual is not None and fused is None:
@@ -544,7 +545,6 @@ def gemm_act(rt: "Runtime", A, B, out, M, N, Kd, lda, ldb, ldc, bias=None, rowve
 
     tuned_call(rt, key, lambda: _nt_candidates(M, N, Kd, splittable and dual is None, staged=True) if dual is None else _dual_candidates(M, N, Kd),
                lambda: choose_cfg(rt, M, N, Kd, ldc, 0 if gather is None else gather.cin, dual is not None and rt.fuse_dual), run)
-    return done[0]
 
 
 def _tile_launched(variant: int, M: int, N: int, split_k: int = 1) -> int:
@@ -650,13 +650,13 @@ class LinearOp:
     # ---- compute ----
     def fwd(self, rt: Runtime, x: torch.Tensor, M: int, res: Optional[torch.Tensor] = None,
             rowvec: Optional[torch.Tensor] = None, rv_ld: int = 0, rv_rpg: int = 0, rv_mod: int = 0,
-            out: Optional[torch.Tensor] = None, dual=None, gn=None):
-        """gn: see gemm_act; with it the return value is (y, statistics taken)."""
+            out: Optional[torch.Tensor] = None, dual=None, gn: Optional[GnStats] = None) -> torch.Tensor:
+        """gn: see gemm_act."""
         y = out if out is not None else rt.empty(M, self.N)
-        took = gemm_act(rt, x, self.w, y, M, self.N, self.Kdim, self.Kdim, self.Kdim, self.N, bias=self.b,
-                        rowvec=rowvec, rv_ld=rv_ld, rv_rpg=rv_rpg, rv_mod=rv_mod, res=res,
-                        ldres=self.N if res is not None else 0, dual=dual, gn=gn)
-        return y if gn is None else (y, took)
+        gemm_act(rt, x, self.w, y, M, self.N, self.Kdim, self.Kdim, self.Kdim, self.N, bias=self.b,
+                 rowvec=rowvec, rv_ld=rv_ld, rv_rpg=rv_rpg, rv_mod=rv_mod, res=res,
+                 ldres=self.N if res is not None else 0, dual=dual, gn=gn)
+        return y
 
     def bwd_dx(self, rt: Runtime, dy: torch.Tensor, M: int, out: Optional[torch.Tensor] = None, dual=None) -> torch.Tensor:
         dx = out if out is not None else rt.empty(M, self.Kdim)
@@ -1073,9 +1073,9 @@ class ConvOp:
 
     def fwd(self, rt: Runtime, x: torch.Tensor, n_img: int, h: int, w: int, T: int = 0,
             res: Optional[torch.Tensor] = None, rowvec=None, rv_ld=0, rv_rpg=0, ldc: Optional[int] = None,
-            out: Optional[torch.Tensor] = None, gn=None):
+            out: Optional[torch.Tensor] = None, gn: Optional[GnStats] = None):
         """x: [n_img*h*w, cin_p] (t3: n_img = B, rows = B*T*h*w).  Returns ([M, cout], ho, wo); `out` [M, ldc]: write the cout
-        columns into the caller's (wider) rows instead of a fresh tensor."""
+        columns into the caller's (wider) rows instead of a fresh tensor.  gn: see gemm_act."""
         ho, wo = self.out_hw(h, w)
         if self.kind == "t3":
             M = n_img * T * h * w
@@ -1086,8 +1086,8 @@ class ConvOp:
         ldc = ldc or self.cout
         y = out if out is not None else rt.empty(M, ldc)
         Kd = self.taps * self.cin_p
-        self.took_gn = gemm_act(rt, x, self.w, y, M, self.cout, Kd, self.cin_p, Kd, ldc, bias=self.b, rowvec=rowvec, rv_ld=rv_ld,
-                                rv_rpg=rv_rpg, res=res, ldres=self.cout if res is not None else 0, gather=g, gn=gn)
+        gemm_act(rt, x, self.w, y, M, self.cout, Kd, self.cin_p, Kd, ldc, bias=self.b, rowvec=rowvec, rv_ld=rv_ld,
+                 rv_rpg=rv_rpg, res=res, ldres=self.cout if res is not None else 0, gather=g, gn=gn)
         return y, ho, wo
 
     def bwd_dx(self, rt: Runtime, dy: torch.Tensor, n_img: int, h: int, w: int, T: int = 0) -> torch.Tensor:
@@ -1119,6 +1119,17 @@ class ConvOp:
 # --------------------------------------------------------------------------------------------------
 # norms
 # --------------------------------------------------------------------------------------------------
+@dataclass
+class GnStats:
+    """GroupNorm statistics of ONE tensor, handed from the GEMM that writes it to the norm that reads it: `GroupNormOp.want` makes the
+    handle, the producer gets it as `gn` (gemm_act sets `filled` when its launch took the statistics), the norm gets it as `pre`.
+    Per call and per tensor: never kept on an op or a module."""
+    stats: torch.Tensor        # zeroed opaque buffer of svdx_gn_stats
+    rows: int                  # a sample is `rows` consecutive rows ...
+    cg: int                    # ... a group `cg` consecutive channels
+    filled: bool = False
+
+
 class GroupNormOp:
     """GroupNorm(32, C) (+ fused SiLU).  n_s samples of `rows` rows: 2-D norm -> sample = frame,
     3-D (TemporalResnetBlock) -> sample = clip with rows = T*HW (the group spans all frames)."""
@@ -1129,30 +1140,27 @@ class GroupNormOp:
         if mod.weight.requires_grad:
             raise NotImplementedError("GroupNorm affine grads are outside this round's trainable set")
 
-    def want(self, rt: Runtime, n_s: int, rows: int):
-        """-> (stats, rows, cg): what the GEMM that writes this norm's input gets as `gn` (ops.gemm_act) so that the statistics are
-        there when `fwd(..., pre=)` runs.  The buffer is a zeroed slice of the sweep's arena; None when the fusion is switched off."""
+    def want(self, rt: Runtime, n_s: int, rows: int) -> Optional[GnStats]:
+        """What the GEMM that writes this norm's input gets as `gn` (ops.gemm_act) so that the statistics are there when `fwd(..., pre=)`
+        runs.  The buffer is a zeroed slice of the sweep's arena; None when the fusion is switched off."""
         if not rt.fuse_gn_stats:
             return None
         stats, pz = rt.take_zeroed(K.GN_REPLICAS * n_s * GN_GROUPS * K.GN_STAT_FLOATS)
         if not pz:
             rt.k.zero(stats)
-        return stats, rows, self.C // GN_GROUPS
+        return GnStats(stats, rows, self.C // GN_GROUPS)
 
-    def fwd(self, rt: Runtime, x: torch.Tensor, n_s: int, rows: int, pre=None):
-        """pre = (stats buffer from `want`, filled): filled -- the GEMM that wrote x took the statistics; not filled -- the (zeroed)
-        buffer is used for the pass over x here.  None: a buffer of this norm's own."""
+    def fwd(self, rt: Runtime, x: torch.Tensor, n_s: int, rows: int, pre: Optional[GnStats] = None):
+        """pre: the handle `want` made for x.  Filled -- the GEMM that wrote x took the statistics; not filled -- its (zeroed) buffer is
+        used for the pass over x here.  None: a buffer of this norm's own."""
         y = rt.empty(n_s * rows, self.C)
         if pre is not None:
-            stats, filled = pre
-            if not filled:
-                rt.k.gn_stats(x, stats, n_s, rows, self.C, GN_GROUPS, prezeroed=1)
-            rt.k.gn_apply(x, stats, self.mod.weight.data, self.mod.bias.data, y, n_s, rows, self.C, GN_GROUPS, self.eps, self.silu)
-            return y, stats
-        stats, pz = rt.take_zeroed(K.GN_REPLICAS * n_s * GN_GROUPS * K.GN_STAT_FLOATS)
-        rt.k.gn_stats(x, stats, n_s, rows, self.C, GN_GROUPS, prezeroed=pz)
-        rt.k.gn_apply(x, stats, self.mod.weight.data, self.mod.bias.data, y, n_s, rows, self.C, GN_GROUPS,
-                      self.eps, self.silu)
+            stats, pz, filled = pre.stats, 1, pre.filled
+        else:
+            (stats, pz), filled = rt.take_zeroed(K.GN_REPLICAS * n_s * GN_GROUPS * K.GN_STAT_FLOATS), False
+        if not filled:
+            rt.k.gn_stats(x, stats, n_s, rows, self.C, GN_GROUPS, prezeroed=pz)
+        rt.k.gn_apply(x, stats, self.mod.weight.data, self.mod.bias.data, y, n_s, rows, self.C, GN_GROUPS, self.eps, self.silu)
         return y, stats
 
     def bwd(self, rt: Runtime, dy, x, stats, n_s: int, rows: int, add: Optional[torch.Tensor] = None):

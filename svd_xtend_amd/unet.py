@@ -25,6 +25,7 @@ from .lora import LoraLinear, base_linear, inject
 from .ops import _ones as ops_ones
 from .ops import (ConvOp, GroupNormOp, LayerNormOp, LinearOp, LoraOp, Runtime, SmallLinearOp, SmallLoraOp, choose_geglu_variant, geglu_candidates, choose_split, flatten_trainables, tuned_call,
                   rup)
+from .pretrained import CONFIG_NAME, WEIGHTS_NAME, FrozenConfig, PretrainedMixin  # noqa: F401  (re-exported: checkpoint.py, training_utils.py)
 
 HEAD_DIM = 64
 
@@ -369,6 +370,9 @@ class BasicTransformerBlock(nn.Module):
         self.sv = (h, st1, qkv, o, lse, h2, st3, pre, n1, xs_qkv, xs_o, cv, ctx)
         return h3
 
+    def drop_saved(self):
+        self.sv = None
+
     def bwd(self, rt: Runtime, dh3, g: Geom, need_dx: bool = True):
         k, C, M, S = rt.k, self.dim, g.M, g.HW
         h, st1, qkv, o, lse, h2, st3, pre, n1, xs_qkv, xs_o, cv, ctx = self.sv
@@ -486,6 +490,9 @@ class TemporalBasicTransformerBlock(nn.Module):
         self.sv = (x, st0, n0, pre0, g0, h, st1, n1, qkv, o, cv, tctx, h1, st3, n3, pre, gg, xs_qkv, xs_o)
         return out
 
+    def drop_saved(self):
+        self.sv = None
+
     def bwd(self, rt: Runtime, dout, g: Geom, need_dx: bool = True, add: Optional[torch.Tensor] = None, add_scale: float = 1.0):
         """returns d(input) + add_scale * add (the fan-in is folded into the last LayerNorm backward)."""
         k, C, M = rt.k, self.dim, g.M
@@ -591,8 +598,8 @@ class TransformerSpatioTemporalModel(nn.Module):
     def fwd(self, rt: Runtime, x, g: Geom, ctx, pre=None, want_out=None):
         """x [M, C]; ctx float [B, cross_dim] (the CLIP embed of each clip; identical for all its frames, so
         the first-frame `time_context` of the temporal blocks is the same tensor).
-        pre: GroupNorm statistics of x left by the GEMM that wrote it (GroupNormOp.fwd); want_out: `gn` operand for the GEMM that writes
-        the result (GroupNormOp.want of the consumer).  Returns (out, statistics of out taken)."""
+        pre: the statistics handle of x (ops.GnStats: what the caller asked of the GEMM that wrote x); want_out: the handle of the
+        result, from GroupNormOp.want of its consumer -- handed to the GEMM that writes it, which marks it filled."""
         k, C, M = rt.k, self.C, g.M
         xn, st = self.gn.fwd(rt, x, g.N, g.HW, pre=pre)
         h = self.pin.fwd(rt, xn, M)
@@ -614,12 +621,24 @@ class TransformerSpatioTemporalModel(nn.Module):
             h2 = rt.empty(M, C)
             k.blend(h, hm, self.time_mixer.mix_factor.data, h2, M * C)
             h = h2
-        if want_out is not None:
-            out, took = self.pout.fwd(rt, h, M, res=x, gn=want_out)
-        else:
-            out, took = self.pout.fwd(rt, h, M, res=x), False
+        out = self.pout.fwd(rt, h, M, res=x, gn=want_out)
         self.sv = (x, st)
-        return out, took
+        return out
+
+    def drop_cross_pre(self):
+        """Cross-attention vectors a sweep precomputed and never consumed (a forward that raised, a knob that flipped between sweeps):
+        the next cross_vec must not read results of an older context."""
+        for b in list(self.transformer_blocks) + list(self.temporal_transformer_blocks):
+            b.attn2._pre = None
+
+    def drop_saved(self):
+        """Forget what the forward kept for a backward that will not run: this module's, its blocks', the pending cross vectors.
+        (Also called by the backward sweep: cross_vec has consumed every pending vector by then, so nothing is freed there; after a
+        knob flipped mid-step the leftovers go then instead of at the head of the next sweep -- harmless.)"""
+        self.sv = None
+        for b in list(self.transformer_blocks) + list(self.temporal_transformer_blocks):
+            b.drop_saved()
+        self.drop_cross_pre()
 
     def bwd(self, rt: Runtime, dout, g: Geom):
         k, C, M = rt.k, self.C, g.M
@@ -638,7 +657,7 @@ class TransformerSpatioTemporalModel(nn.Module):
             dh = tblk.bwd(rt, dhm, g, need_dx=not stop, add=None if stop else dh, add_scale=self.alpha)
             del dhm
             if stop:
-                blk.sv = None
+                blk.drop_saved()
                 return None
             dh = blk.bwd(rt, dh, g, need_dx=not last)    # with adapters (config 5) the spatial block has gradients of its own
             if last:
@@ -692,8 +711,8 @@ class _ResnetHalf(nn.Module):
         return (g.B, g.T * g.HW) if self.temporal else (g.N, g.HW)
 
     def fwd(self, rt: Runtime, x, g: Geom, temb_all, pre=None, want_out=None):
-        """pre / want_out: GroupNorm statistics from the producing GEMM's store loop -- of x (already taken) and of the result (asked
-        of conv2) -- see TransformerSpatioTemporalModel.fwd.  Returns (out, statistics of out taken)."""
+        """pre / want_out: GroupNorm statistics handles -- of x (asked of the GEMM that wrote it) and of the result (asked of conv2) --
+        see TransformerSpatioTemporalModel.fwd."""
         n_s, rows = self._ns(g)
         a1, st1 = self.gn1.fwd(rt, x, n_s, rows, pre=pre)
         off, ld = self.temb_slice
@@ -701,11 +720,14 @@ class _ResnetHalf(nn.Module):
         w2 = self.gn2.want(rt, n_s, rows)
         h1, _, _ = self.c1.fwd(rt, a1, ni, g.h, g.w, T=g.T, rowvec=temb_all[:, off:], rv_ld=ld, rv_rpg=g.T * g.HW, gn=w2)
         del a1
-        a2, st2 = self.gn2.fwd(rt, h1, n_s, rows, pre=None if w2 is None else (w2[0], self.c1.took_gn))
+        a2, st2 = self.gn2.fwd(rt, h1, n_s, rows, pre=w2)
         sc = x if self.sc is None else self.sc.fwd(rt, x, ni, g.h, g.w, T=g.T)[0]
         out, _, _ = self.c2.fwd(rt, a2, ni, g.h, g.w, T=g.T, res=sc, gn=want_out)
         self.sv = (x, st1, h1, st2)
-        return out, (want_out is not None and self.c2.took_gn)
+        return out
+
+    def drop_saved(self):
+        self.sv = None
 
     def bwd(self, rt: Runtime, dout, g: Geom, add=None):
         """returns dx (+ add).  The identity/1x1 shortcut gradient is folded into the last GroupNorm backward."""
@@ -763,12 +785,16 @@ class SpatioTemporalResBlock(nn.Module):
     def fwd(self, rt: Runtime, x, g: Geom, temb_all, pre=None, want_out=None):
         t = self.temporal_res_block
         ws = t.gn1.want(rt, *t._ns(g))            # the temporal half's first norm reads the spatial half's output (clip-wide groups)
-        s, took = self.spatial_res_block.fwd(rt, x, g, temb_all, pre=pre, want_out=ws)
-        return t.fwd(rt, s, g, temb_all, pre=None if ws is None else (ws[0], took), want_out=want_out)
+        s = self.spatial_res_block.fwd(rt, x, g, temb_all, pre=pre, want_out=ws)
+        return t.fwd(rt, s, g, temb_all, pre=ws, want_out=want_out)
+
+    def drop_saved(self):
+        self.spatial_res_block.drop_saved()
+        self.temporal_res_block.drop_saved()
 
     def bwd(self, rt: Runtime, dout, g: Geom):
         if not self.need_dx:
-            self.spatial_res_block.sv = self.temporal_res_block.sv = None
+            self.drop_saved()
             return None
         ds_total = self.temporal_res_block.bwd(rt, dout, g)
         return self.spatial_res_block.bwd(rt, ds_total, g)
@@ -820,21 +846,6 @@ class UNetSpatioTemporalConditionOutput(SimpleNamespace):
     pass
 
 
-class FrozenConfig(dict):
-    """diffusers' FrozenDict in miniature: `config.addition_time_embed_dim` (train_svd.py:887) and
-    `model.register_to_config(**other.config)` (train_svd.py:723) both work."""
-
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError as e:
-            raise AttributeError(k) from e
-
-
-CONFIG_NAME = "config.json"
-WEIGHTS_NAME = "diffusion_pytorch_model{variant}.safetensors"
-
-
 class _UNetFn(torch.autograd.Function):
     """Thin autograd boundary so `loss.backward()` in a host script reaches the hand-written backward."""
 
@@ -849,8 +860,10 @@ class _UNetFn(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
-class UNetSpatioTemporalConditionModel(nn.Module):
-    """Constructor signature of src/unet_spatio_temporal_condition.py:71-96."""
+class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
+    """Constructor signature of src/unet_spatio_temporal_condition.py:71-96.  `from_pretrained` reads the diffusers folder layout
+    (train_svd.py:651-656, 721): `<path>/<subfolder>/config.json` + `diffusion_pytorch_model[.<variant>].safetensors`, diffusers key
+    names, strict load."""
 
     _supports_gradient_checkpointing = True
 
@@ -962,27 +975,8 @@ class UNetSpatioTemporalConditionModel(nn.Module):
         return cls(**{k: v for k, v in dict(config).items() if k in names and not k.startswith("_")})
 
     @classmethod
-    def from_pretrained(cls, path, subfolder: Optional[str] = None, variant: Optional[str] = None, torch_dtype=None,
-                        **unused):
-        """diffusers folder layout (train_svd.py:651-656, 721): `<path>/<subfolder>/config.json` +
-        `diffusion_pytorch_model[.<variant>].safetensors`, diffusers key names, strict load.  Local folders only."""
-        import json
-        import os
-
-        from safetensors.torch import load_file
-        folder = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(folder, CONFIG_NAME)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
-        ctor = {k: v for k, v in cfg.items() if k in cls.__init__.__code__.co_varnames}
-        model = cls(**ctor)
-        wpath = os.path.join(folder, WEIGHTS_NAME.format(variant=f".{variant}" if variant else ""))
-        if not os.path.exists(wpath) and variant:                         # diffusers falls back to the un-suffixed file
-            wpath = os.path.join(folder, WEIGHTS_NAME.format(variant=""))
-        sd = load_file(wpath)
-        model.load_state_dict({k: v.float() for k, v in sd.items()}, strict=True)   # float masters; kernels use packed copies
-        if torch_dtype is not None and torch_dtype != torch.float32:
-            model._requested_dtype = torch_dtype
-        return model
+    def _config_args(cls, raw):
+        return {k: v for k, v in super()._config_args(raw).items() if k in cls.__init__.__code__.co_varnames}
 
     def save_pretrained(self, folder, variant: Optional[str] = None, **unused) -> None:    # train_svd.py:703, 1088-1090
         import json
@@ -1076,26 +1070,11 @@ class UNetSpatioTemporalConditionModel(nn.Module):
                 steps.append(("up", blk.upsamplers[0]))
         return steps
 
-    def to(self, *args, **kwargs):
-        """`unet.to(device, dtype=weight_dtype)` (train_svd_lora.py:669, train_svd.py:739): the float masters stay fp32 (the
-        kernels run on their packed 16-bit copies); a half / bfloat16 request only selects the activation dtype."""
-        device, dtype, non_blocking, _ = torch._C._nn._parse_to(*args, **kwargs)
-        if dtype is not None and dtype.is_floating_point and dtype != torch.float32:
-            self._requested_dtype = dtype
-            return super().to(device=device, non_blocking=non_blocking) if device is not None else self
-        return super().to(*args, **kwargs)
-
-    def half(self):
-        return self.to(dtype=torch.float16)
-
-    def bfloat16(self):
-        return self.to(dtype=torch.bfloat16)
-
     def prepare(self, dtype: Optional[torch.dtype] = None) -> "UNetSpatioTemporalConditionModel":
         """Build operator objects and pack weights into kernel layouts.  Call after weights are loaded, after
         `requires_grad` flags are final and (for training) after the Trainer has installed flat grads.  dtype: activation
         dtype (default: what `.to(dtype=...)` / `from_pretrained(torch_dtype=...)` asked for, else float16)."""
-        dtype = dtype or getattr(self, "_requested_dtype", None) or torch.float16
+        dtype = dtype or self._requested_dtype or torch.float16
         dev = next(self.parameters()).device
         if any(p.requires_grad and p.grad is None for p in self.parameters()):
             # stand-alone use (host script keeps its own optimizer): give the trainables flat, adjacent storage
@@ -1180,22 +1159,14 @@ class UNetSpatioTemporalConditionModel(nn.Module):
 
     def _drop_saved(self):
         for kind, m in self.steps:
-            if kind == "res":
-                m.spatial_res_block.sv = m.temporal_res_block.sv = None
-            elif kind == "attn":
-                m.sv = None
-                for b in list(m.transformer_blocks) + list(m.temporal_transformer_blocks):
-                    b.sv = None
+            if kind in ("res", "attn"):
+                m.drop_saved()
         self._fwd_state = None
-        self._clear_cross_pre()
 
     def _clear_cross_pre(self):
-        """Drop cross-attention vectors a previous sweep precomputed and never consumed (a forward that raised, a knob that
-        flipped between sweeps): the next cross_vec must not read results of an older context."""
         for kind, m in self.steps:
             if kind == "attn":
-                for b in list(m.transformer_blocks) + list(m.temporal_transformer_blocks):
-                    b.attn2._pre = None
+                m.drop_cross_pre()
 
     def _forward_impl(self, sample, timestep, ehs, added_time_ids):
         out_rows = self.forward_rows(sample, timestep, ehs, added_time_ids)
@@ -1261,9 +1232,10 @@ class UNetSpatioTemporalConditionModel(nn.Module):
         x0 = rt.empty(g.M, self.cin_pad)
         k.nchw_to_rows(sample.reshape(g.N, Cin, h, w).to(torch.float32).contiguous(), x0, g.N, Cin, h, w,
                        self.cin_pad, 1.0)
-        # GroupNorm statistics ride on the GEMM that writes the normalised tensor (svdx_gemm_gn): `consumer(i, geom)` is the `gn` operand
-        # for the producer at step i -- the first norm of the next module when that module reads the tensor as it stands (a skip
-        # connection is concatenated first: its norm spans both inputs and takes its own pass), the output norm after the last step
+        # GroupNorm statistics ride on the GEMM that writes the normalised tensor (svdx_gemm_gn): `consumer(i, geom)` is the handle
+        # (ops.GnStats) the producer at step i gets as `gn` and the reader of its output as `pre` -- made by the first norm of the next
+        # module when that module reads the tensor as it stands (a skip connection is concatenated first: its norm spans both inputs
+        # and takes its own pass), by the output norm after the last step
         steps = self.steps
 
         def consumer(i, geom):
@@ -1276,9 +1248,8 @@ class UNetSpatioTemporalConditionModel(nn.Module):
                 op, n_s, rows = steps[j][1].first_norm(geom)
                 return op.want(rt, n_s, rows)
             return None
-        want = consumer(-1, g)
-        x, _, _ = self.cin_op.fwd(rt, x0, g.N, h, w, gn=want)
-        pre = None if want is None else (want[0], self.cin_op.took_gn)      # (statistics buffer, filled) of x for the next first norm
+        pre = consumer(-1, g)                  # the statistics handle of x, here and below
+        x, _, _ = self.cin_op.fwd(rt, x0, g.N, h, w, gn=pre)
         del x0
 
         skips: List[Tuple[torch.Tensor, Geom]] = [(x, g)]
@@ -1288,16 +1259,15 @@ class UNetSpatioTemporalConditionModel(nn.Module):
         for i, (kind, m) in enumerate(steps):
             if kind == "res" or kind == "attn":
                 want = consumer(i, cur)
-                x, took = m.fwd(rt, x, cur, temb_all if kind == "res" else ctx, pre=pre, want_out=want)
-                pre = None if want is None else (want[0], took)
+                x = m.fwd(rt, x, cur, temb_all if kind == "res" else ctx, pre=pre, want_out=want)
+                pre = want
             elif kind == "push":
                 skips.append((x, cur))
             elif kind == "down" or kind == "up":
                 ho, wo = m.op.out_hw(cur.h, cur.w)
                 nxt = Geom(B, T, ho, wo)
-                want = consumer(i, nxt)
-                x, ho, wo = m.op.fwd(rt, x, cur.N, cur.h, cur.w, gn=want)
-                pre = None if want is None else (want[0], m.op.took_gn)
+                pre = consumer(i, nxt)
+                x, ho, wo = m.op.fwd(rt, x, cur.N, cur.h, cur.w, gn=pre)
                 cur = nxt
                 if kind == "down":
                     geoms.append(cur)
@@ -1413,12 +1383,8 @@ class UNetSpatioTemporalConditionModel(nn.Module):
                 lvl -= 1
             if dx is None:
                 cur = level_geoms[lvl]
-                if kind == "res":
-                    m.spatial_res_block.sv = m.temporal_res_block.sv = None
-                elif kind == "attn":
-                    m.sv = None
-                    for b in list(m.transformer_blocks) + list(m.temporal_transformer_blocks):
-                        b.sv = None
+                if kind in ("res", "attn"):
+                    m.drop_saved()
                 continue
             if kind == "res" or kind == "attn":
                 dx = m.bwd(rt, dx, cur)

@@ -26,8 +26,6 @@ Conv3d (3,1,1) `time_conv_out`.  A SpatioTemporalResBlock here has no time embed
 resnet's residual branch -- the factor is folded into the temporal conv2 weights at prepare() (as in the UNet's resnets)."""
 from __future__ import annotations
 
-import json
-import os
 from types import SimpleNamespace
 from typing import Optional, Sequence
 
@@ -36,10 +34,7 @@ import torch.nn as nn
 
 from . import kernels as K
 from .ops import ConvOp, GroupNormOp, LinearOp, Runtime, gemm_act, rup
-from .unet import FrozenConfig
-
-CONFIG_NAME = "config.json"
-WEIGHTS_NAME = "diffusion_pytorch_model{variant}.safetensors"
+from .pretrained import FrozenConfig, PretrainedMixin
 
 
 class _Resnet(nn.Module):
@@ -63,17 +58,15 @@ class _Resnet(nn.Module):
                 op.pack(rt, need_dx=False)
 
     def fwd(self, rt: Runtime, x, n: int, h: int, w: int, pre=None, want_out=None):
-        """pre: (stats, filled) when the launch that wrote x already took norm1's statistics (GroupNormOp.fwd); want_out: what the norm
-        that reads THIS block's output wants from the launch that writes it (GroupNormOp.want) -- `self.took_out` says whether it got them.
-        As in the UNet's resnets, the statistics passes over the full-resolution tensors ride on the producing GEMM's store loop."""
+        """pre: the statistics handle of x (ops.GnStats, asked of the launch that wrote x for norm1); want_out: the handle the norm that
+        reads THIS block's output made (GroupNormOp.want), for the launch that writes it.  As in the UNet's resnets, the statistics
+        passes over the full-resolution tensors ride on the producing GEMM's store loop."""
         a, _ = self.gn1.fwd(rt, x, n, h * w, pre=pre)
         w2 = self.gn2.want(rt, n, h * w)
         y, _, _ = self.c1.fwd(rt, a, n, h, w, gn=w2)
-        a, _ = self.gn2.fwd(rt, y, n, h * w, pre=(w2[0], self.c1.took_gn) if w2 is not None else None)
+        a, _ = self.gn2.fwd(rt, y, n, h * w, pre=w2)
         sc = x if self.sc is None else self.sc.fwd(rt, x, n, h, w)[0]
-        out = self.c2.fwd(rt, a, n, h, w, res=sc, gn=want_out)[0]
-        self.took_out = want_out is not None and self.c2.took_gn
-        return out
+        return self.c2.fwd(rt, a, n, h, w, res=sc, gn=want_out)[0]
 
 
 class _Downsample(nn.Module):
@@ -267,9 +260,10 @@ class DiagonalGaussianDistribution:
         return self.mean
 
 
-class AutoencoderKLTemporalDecoder(nn.Module):
+class AutoencoderKLTemporalDecoder(PretrainedMixin, nn.Module):
     """Constructor arguments of the diffusers class that shape the ENCODER (everything else in a `vae/config.json` is accepted and
-    kept in `.config`)."""
+    kept in `.config`).  `from_pretrained`: `<path>/<subfolder>/config.json` + `diffusion_pytorch_model[.<variant>].safetensors`
+    (train_svd.py:649-650), loaded strictly (encoder, decoder, quant_conv)."""
 
     def __init__(self, in_channels: int = 3, out_channels: int = 3, latent_channels: int = 4,
                  block_out_channels: Sequence[int] = (128, 256, 512, 512), layers_per_block: int = 2,
@@ -285,34 +279,6 @@ class AutoencoderKLTemporalDecoder(nn.Module):
         self.decoder = _Decoder(latent_channels, out_channels, block_out_channels, layers_per_block)
         self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
         self.rt: Optional[Runtime] = None
-        self._requested_dtype = None
-
-    # ---- loading ------------------------------------------------------------------------------------------------------
-    @classmethod
-    def from_pretrained(cls, path, subfolder: Optional[str] = None, variant: Optional[str] = None, torch_dtype=None, **unused):
-        """`<path>/<subfolder>/config.json` + `diffusion_pytorch_model[.<variant>].safetensors` (train_svd.py:649-650), loaded
-        strictly (encoder, decoder, quant_conv)."""
-        from safetensors.torch import load_file
-        folder = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(folder, CONFIG_NAME)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
-        model = cls(**cfg)
-        wpath = os.path.join(folder, WEIGHTS_NAME.format(variant=f".{variant}" if variant else ""))
-        if not os.path.exists(wpath) and variant:
-            wpath = os.path.join(folder, WEIGHTS_NAME.format(variant=""))
-        sd = {k: v.float() for k, v in load_file(wpath).items()}
-        model.load_state_dict(sd, strict=True)
-        if torch_dtype is not None and torch_dtype != torch.float32:
-            model._requested_dtype = torch_dtype
-        return model
-
-    def to(self, *args, **kwargs):
-        """`vae.to(device, dtype=weight_dtype)` (train_svd.py:738): float masters stay fp32, a 16-bit dtype selects the activation type."""
-        device, dtype, non_blocking, _ = torch._C._nn._parse_to(*args, **kwargs)
-        if dtype is not None and dtype.is_floating_point and dtype != torch.float32:
-            self._requested_dtype = dtype
-            return super().to(device=device, non_blocking=non_blocking) if device is not None else self
-        return super().to(*args, **kwargs)
 
     # ---- packing ------------------------------------------------------------------------------------------------------
     def prepare(self, dtype: Optional[torch.dtype] = None) -> "AutoencoderKLTemporalDecoder":
@@ -391,9 +357,8 @@ class AutoencoderKLTemporalDecoder(nn.Module):
         # stage's first GroupNorm wants, so that the statistics passes over the full-resolution tensors ride on the producing GEMMs
         blocks = list(enc.down_blocks)
         mid = enc.mid_block
-        first = blocks[0].resnets[0].gn1.want(rt, n, H * W)
-        took = gemm_act(rt, a, self.w_in, y, n * H * W, c0, self.k_in, self.k_in, self.k_in, c0, bias=enc.conv_in.bias.data, gn=first)
-        pre = (first[0], took) if first is not None else None
+        pre = blocks[0].resnets[0].gn1.want(rt, n, H * W)            # the statistics handle of y, here and below
+        gemm_act(rt, a, self.w_in, y, n * H * W, c0, self.k_in, self.k_in, self.k_in, c0, bias=enc.conv_in.bias.data, gn=pre)
         del a
         h, w = H, W
         for bi, blk in enumerate(blocks):
@@ -403,17 +368,16 @@ class AutoencoderKLTemporalDecoder(nn.Module):
             for i, r in enumerate(rs):
                 nxt = rs[i + 1].gn1.want(rt, n, h * w) if i + 1 < len(rs) else (after.want(rt, n, h * w) if down is None else None)
                 y = r.fwd(rt, y, n, h, w, pre=pre, want_out=nxt)
-                pre = (nxt[0], r.took_out) if nxt is not None else None
+                pre = nxt
             if down is not None:
                 ho, wo = down.out_hw(h, w)
-                nxt = after.want(rt, n, ho * wo)
-                y, h, w = down.fwd(rt, y, n, h, w, gn=nxt)
-                pre = (nxt[0], down.took_gn) if nxt is not None else None
+                pre = after.want(rt, n, ho * wo)
+                y, h, w = down.fwd(rt, y, n, h, w, gn=pre)
         y = mid.resnets[0].fwd(rt, y, n, h, w, pre=pre)
         y = mid.attentions[0].fwd(rt, y, n, h, w)
         want = self.gn_out.want(rt, n, h * w)
         y = mid.resnets[1].fwd(rt, y, n, h, w, want_out=want)
-        a, _ = self.gn_out.fwd(rt, y, n, h * w, pre=(want[0], mid.resnets[1].took_out) if want is not None else None)
+        a, _ = self.gn_out.fwd(rt, y, n, h * w, pre=want)
         return self.c_out.fwd(rt, a, n, h, w)[0], h, w
 
     def max_frames(self, H: int, W: int) -> int:

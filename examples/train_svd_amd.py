@@ -7,6 +7,7 @@ accelerate (device placement, mixed precision, DDP, save_state / load_state) is 
     python examples/train_svd_amd.py --max_train_steps 10 --output_dir /tmp/svd_out                        # synthetic clips, random init
     python examples/train_svd_amd.py --pretrained_model_name_or_path <svd folder> --base_folder <frames>   # as the reference
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_svd_amd.py ...
+    python examples/train_svd_amd.py --base_folder <frames> --latent_cache <dir> ...                         # encode every frame once, train from the store
 
 Without `--pretrained_model_name_or_path` the three models are built at the SVD configuration with random weights (there is no
 network here); without `--base_folder` the clips are synthetic U(-1, 1) pixels of the requested shape (the range of the
@@ -72,6 +73,11 @@ def parse_args(argv=None):
     ap.add_argument("--reference_rng", action="store_true",
                     help="draw cond_sigmas / sigmas the reference's way (host, process-global generator, train_svd.py:954 / :964): with --seed the run "
                          "walks the reference's sigma sequence")
+    ap.add_argument("--latent_cache", default=None, metavar="DIR",
+                    help="train from stored VAE posteriors and CLIP embeddings (svd_xtend_amd/latent_cache.py): DIR is loaded and checked against the "
+                         "loaded towers when it holds a cache, otherwise one is built from every folder of --base_folder (or --cache_videos synthetic "
+                         "videos) and saved there")
+    ap.add_argument("--cache_videos", type=int, default=8, help="synthetic videos of a latent cache built without --base_folder")
     return ap.parse_args(argv)
 
 
@@ -114,6 +120,80 @@ class FrameFolders(torch.utils.data.Dataset):
                 t = torch.from_numpy(np.array(img.convert("RGB").resize((self.w, self.h)))).float()
             out[i] = (t / 127.5 - 1).permute(2, 0, 1)
         return {"pixel_values": out}
+
+
+def load_frame(path, width, height):
+    from PIL import Image
+    with Image.open(path) as img:
+        t = torch.from_numpy(np.array(img.convert("RGB").resize((width, height)))).float()
+    return (t / 127.5 - 1).permute(2, 0, 1)
+
+
+class CachedSyntheticClips(torch.utils.data.Dataset):
+    """SyntheticClips over a latent cache: `n_videos` seeded U(-1, 1) videos of 2 * sample_frames frames; an item is a (video, start)
+    drawn from the generator SyntheticClips seeds for that index -- the first frame's pixels and the window's cache row."""
+
+    def __init__(self, num_samples, width, height, sample_frames, seed, n_videos, cache=None):
+        self.n, self.shape, self.seed, self.f = num_samples, (3, height, width), seed, sample_frames
+        self.n_videos, self.length, self.cache = n_videos, 2 * sample_frames, cache
+        self.draw_seed = seed                                  # of the (video, start) draws; `seed` is the videos' content
+
+    def frame(self, video, i):
+        g = torch.Generator().manual_seed((self.seed * 1000003 + video) * 1000003 + i)
+        return torch.rand(self.shape, generator=g) * 2 - 1
+
+    def videos(self):
+        for v in range(self.n_videos):
+            yield torch.stack([self.frame(v, i) for i in range(self.length)])
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, idx):
+        g = torch.Generator().manual_seed(self.draw_seed * 1000003 + idx)
+        v = int(torch.randint(self.n_videos, (1,), generator=g))
+        s = int(torch.randint(self.length - self.f + 1, (1,), generator=g))
+        return {"first_frame": self.frame(v, s), "index": torch.tensor(self.cache.window(v, s, self.f), dtype=torch.int64)}
+
+
+class CachedFrameFolders(FrameFolders):
+    """FrameFolders over a latent cache (video v = folder v in sorted order): the same draw of (folder, start), ONE image opened
+    instead of `sample_frames`."""
+
+    def __init__(self, base_folder, num_samples, width, height, sample_frames, cache=None):
+        super().__init__(base_folder, num_samples, width, height, sample_frames)
+        self.cache = cache
+
+    def videos(self):
+        for name in self.folders:
+            folder = os.path.join(self.base, name)
+            yield torch.stack([load_frame(os.path.join(folder, f), self.w, self.h) for f in sorted(os.listdir(folder))])
+
+    def __getitem__(self, idx):
+        name = random.choice(self.folders)
+        folder = os.path.join(self.base, name)
+        frames = sorted(os.listdir(folder))
+        if len(frames) < self.f:
+            raise ValueError(f"The selected folder '{folder}' contains fewer than `{self.f}` frames.")
+        s = random.randint(0, len(frames) - self.f)
+        return {"first_frame": load_frame(os.path.join(folder, frames[s]), self.w, self.h),
+                "index": torch.tensor(self.cache.window(self.folders.index(name), s, self.f), dtype=torch.int64)}
+
+
+def open_latent_cache(args, dataset, vae, image_encoder, dev, is_main, world):
+    """--latent_cache DIR: load and check the cache DIR holds, or build it from the dataset's videos on rank 0 and save it there."""
+    from svd_xtend_amd.latent_cache import LatentCache
+    if is_main and not LatentCache.exists(args.latent_cache):
+        t0 = time.perf_counter()
+        cache = LatentCache.build(vae, image_encoder, dataset.videos())
+        cache.save(args.latent_cache)
+        print(f"Built a latent cache of {cache.n_frames} frames in {cache.n_videos} videos in {time.perf_counter() - t0:.1f} s: {args.latent_cache}", flush=True)
+    if world > 1:
+        dist.barrier()                                    # the other ranks load what rank 0 found or wrote
+    cache = LatentCache.load(args.latent_cache, dev, vae=vae, image_encoder=image_encoder, height=args.height, width=args.width)
+    if is_main:
+        print(f"Latent cache {args.latent_cache}: {cache.n_frames} frames in {cache.n_videos} videos", flush=True)
+    return cache
 
 
 TINY = dict(unet=dict(block_out_channels=(64, 128, 128, 128), addition_time_embed_dim=32, projection_class_embeddings_input_dim=96,
@@ -193,8 +273,17 @@ def main(argv=None):
         ema_unet = EMAModel(unet.parameters(), model_cls=UNetSpatioTemporalConditionModel, model_config=unet.config,
                             on_weights_changed=trainer.weights_changed)
 
-    dataset = (FrameFolders(args.base_folder, args.num_samples, args.width, args.height, args.num_frames) if args.base_folder
-               else SyntheticClips(args.num_samples, args.width, args.height, args.num_frames, (args.seed or 0) + rank))
+    cache = None
+    if args.latent_cache:
+        # the synthetic videos are the same on every rank (they are the cache's content); the draw of (video, start) is per rank
+        dataset = (CachedFrameFolders(args.base_folder, args.num_samples, args.width, args.height, args.num_frames) if args.base_folder
+                   else CachedSyntheticClips(args.num_samples, args.width, args.height, args.num_frames, args.seed or 0, args.cache_videos))
+        dataset.cache = cache = open_latent_cache(args, dataset, vae, image_encoder, dev, is_main, world)
+        if not args.base_folder:
+            dataset.draw_seed = (args.seed or 0) + rank
+    else:
+        dataset = (FrameFolders(args.base_folder, args.num_samples, args.width, args.height, args.num_frames) if args.base_folder
+                   else SyntheticClips(args.num_samples, args.width, args.height, args.num_frames, (args.seed or 0) + rank))
     sampler_gen = torch.Generator().manual_seed((args.seed or 0) + rank)
     sampler = torch.utils.data.RandomSampler(dataset, generator=sampler_gen)
     loader = torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=args.per_gpu_batch_size,
@@ -219,7 +308,8 @@ def main(argv=None):
     # batches and restores the generators that drive its noise, train_svd.py:900-931): both streams are re-seeded from (seed, rank, global_step)
     sampler_gen.manual_seed((args.seed or 0) + rank + 1000003 * global_step)
     loop = TrainLoop(trainer, vae, image_encoder, conditioning_dropout_prob=args.conditioning_dropout_prob,
-                     seed=(args.seed or 0) * 7919 + rank + 104729 * global_step, use_graph=not args.no_graph, ema=ema_unet, reference_rng=args.reference_rng)
+                     seed=(args.seed or 0) * 7919 + rank + 104729 * global_step, use_graph=not args.no_graph, ema=ema_unet, reference_rng=args.reference_rng,
+                     latent_cache=cache, num_frames=args.num_frames if cache is not None else None)
 
     def clips():
         while True:
@@ -228,7 +318,8 @@ def main(argv=None):
                 group = []
                 try:
                     for _ in range(args.gradient_accumulation_steps):
-                        group.append(next(it)["pixel_values"])
+                        item = next(it)
+                        group.append(item["pixel_values"] if cache is None else dict(first_frame=item["first_frame"], index=item["index"]))
                 except StopIteration:
                     break
                 yield group

@@ -62,7 +62,7 @@ typedef struct svdx_gather {
 
 /* ABI revision of this header: bumped whenever an entry changes its argument list or meaning (100 = rounds 1-3; 400 = round 4).
  * svdx_version() returns the value the library was built with; the ctypes binding refuses a library whose number differs. */
-#define SVDX_VERSION 611
+#define SVDX_VERSION 612
 int         svdx_version(void);
 int         svdx_last_error(char* buf, size_t n);
 /* 1 when the binary was built for gfx950 and a device is usable */
@@ -460,6 +460,24 @@ int svdx_grad_clip_coef(const double* partial, const int* spans, int n_spans, in
 /* ---- EMA of the trainable weights (diffusers EMAModel.step, train_svd.py:1053-1054): shadow -= one_minus_decay * (shadow - p)
  *      over n floats (both buffers 16-byte aligned).  The decay itself follows EMAModel.get_decay on the host. */
 int svdx_ema_lerp(float* shadow, const float* p, int64_t n, float one_minus_decay, void* stream);
+
+/* ---- one micro-batch of step inputs from a latent cache (svd_xtend_amd/latent_cache.py): window gather, posterior sample, EDM noising
+ *      (train_svd.py:964-972), conditioning dropout (:992-1011) and the channel concat (:1014-1017) in one launch.  All float except `first`.
+ *      mean, std [F, chw]: the cached posterior moments per frame, F = n_frames.  first [B] int64 ON THE DEVICE: the cache row of each
+ *      sample's first frame; the kernel clamps it into [0, F - T], so no device value makes it read outside the cache (rejecting a bad
+ *      index is the host's job: LatentCache.window).  eps [B, T + 1, chw] (row T belongs to the conditioning frame), noise [B, T, chw],
+ *      cond_mean / cond_std [B, chw]: the moments of the freshly encoded noise-augmented first frame; sigma, den = (sigma^2 + 1)^0.5,
+ *      keep (1, or 0 where the dropout zeroes the conditioning latent) [B].  With f = first[b] + t, every line one rounded fp32 operation
+ *      per operator -- no fused multiply-add, IEEE division -- so the outputs equal the torch statements of TrainLoop._compute bit for bit:
+ *        target[b,t]       = (mean[f] + std[f] * eps[b,t]) * scaling
+ *        noisy[b,t]        = target[b,t] + noise[b,t] * sigma[b]
+ *        unet_in[b,t,0]    = noisy[b,t] / den[b]
+ *        unet_in[b,t,1]    = keep[b] * (((cond_mean[b] + cond_std[b] * eps[b,T]) * scaling) / scaling)
+ *      unet_in [B, T, 2, chw], noisy and target [B, T, chw].  16-byte accesses when chw % 4 == 0 and every tensor base is 16-byte aligned,
+ *      a scalar path otherwise.  Errors: a null pointer, B, T or chw < 1, F < T. */
+int svdx_latent_batch(const float* mean, const float* std, int n_frames, const int64_t* first, const float* eps, const float* noise,
+                      const float* cond_mean, const float* cond_std, const float* sigma, const float* den, const float* keep,
+                      float scaling, float* unet_in, float* noisy, float* target, int B, int T, int chw, void* stream);
 
 #ifdef __cplusplus
 }

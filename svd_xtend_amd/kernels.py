@@ -26,7 +26,7 @@ LN_PARTIAL_ROWS = 2048
 GN_REPLICAS = 8
 GN_STAT_FLOATS = 4             # floats of storage per (replica, sample, group) of a GroupNorm statistics buffer: two int64
 GATHER_PLAIN, GATHER_CONV3X3, GATHER_CONV3X3_DGRAD2, GATHER_TEMPORAL3, GATHER_CONV3X3_PAD0 = 0, 1, 2, 3, 4
-ABI_VERSION = 611              # include/svdx.h: SVDX_VERSION this binding was written against
+ABI_VERSION = 612              # include/svdx.h: SVDX_VERSION this binding was written against
 OPT_STATE_FLOATS = 16          # include/svdx.h: layout of the optimizer / loss-scale / schedule state
 SCHED_KINDS = {"constant": 0, "constant_with_warmup": 1, "linear": 2, "cosine": 3, "cosine_with_restarts": 4, "polynomial": 5, "piecewise_constant": 6}
 SCHED_MAX_RULES = 8            # include/svdx.h SVDX_SCHED_MAX_RULES: step rules of piecewise_constant, stored behind the 16 state floats
@@ -143,6 +143,7 @@ _SIGS = {
     "svdx_adamw": "pppp" "l" "dddddd" "pp" "iip",
     "svdx_adamw_tiled": "ppppp" "i" "dddddd" "ppp" "iip",
     "svdx_ema_lerp": "pp" "l" "f" "p",
+    "svdx_latent_batch": "pp" "i" "p" "pp" "pp" "ppp" "f" "ppp" "iii" "p",
     "svdx_grad_sumsq_spans": "pp" "i" "pp",
     "svdx_grad_clip_coef": "pp" "ii" "dd" "pp" "ip",
     "svdx_allreduce_grads": "p" "ii" "l" "i" "p",
@@ -522,6 +523,23 @@ class HipBackend:
 
     def ema_lerp(self, shadow, p, n, one_minus_decay):
         self._call("svdx_ema_lerp", _f32(shadow), _f32(p), n, float(one_minus_decay), self._stream())
+
+    def latent_batch(self, mean, std, first, eps, noise, cond_mean, cond_std, sigma, den, keep, scaling, unet_in, noisy, target):
+        """include/svdx.h svdx_latent_batch: mean / std [F, c, h, w] (the cache), first int64 [B] on the device, eps [B, T + 1, c, h, w],
+        noise [B, T, c, h, w], cond_mean / cond_std [B, c, h, w], sigma / den / keep [B] -> unet_in [B, T, 2c, h, w], noisy, target."""
+        B, T = noise.shape[0], noise.shape[1]
+        chw = noise[0, 0].numel()
+        if first.dtype != torch.int64 or first.numel() != B or not first.is_contiguous():
+            raise SvdxError(f"first must be a contiguous int64 tensor of {B} elements, got {first.dtype} {tuple(first.shape)}")
+        for name, t, numel in (("mean", mean, mean.shape[0] * chw), ("std", std, mean.shape[0] * chw), ("eps", eps, B * (T + 1) * chw),
+                               ("noise", noise, B * T * chw), ("cond_mean", cond_mean, B * chw), ("cond_std", cond_std, B * chw),
+                               ("sigma", sigma, B), ("den", den, B), ("keep", keep, B), ("unet_in", unet_in, 2 * B * T * chw),
+                               ("noisy", noisy, B * T * chw), ("target", target, B * T * chw)):
+            if t.numel() != numel or not t.is_contiguous():
+                raise SvdxError(f"latent_batch: {name} must be contiguous with {numel} elements, got {tuple(t.shape)}")
+        self._call("svdx_latent_batch", _f32(mean), _f32(std), int(mean.shape[0]), first.data_ptr(), _f32(eps), _f32(noise), _f32(cond_mean),
+                   _f32(cond_std), _f32(sigma), _f32(den), _f32(keep), float(scaling), _f32(unet_in), _f32(noisy), _f32(target), B, T, chw,
+                   self._stream())
 
     def grad_sumsq_spans(self, g, spans, n_spans, partial):
         """include/svdx.h svdx_grad_sumsq_spans: spans int32 [n_spans, 3] (offset, count, tensor); partial float64 [>= n_spans]."""

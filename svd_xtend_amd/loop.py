@@ -15,15 +15,20 @@ beside the one gradient all-reduce, on one rank they simply fill the stream whil
 per iteration is the loss read, and it happens after the next clip's work has been queued, so the device never waits for Python.
 Everything random (noise, sigmas, dropout mask) is drawn on the device from one seeded generator; nothing is copied back.
 
+With `latent_cache=` (svd_xtend_amd/latent_cache.py) the window's posterior moments and the image embedding come from a device-resident
+store instead of the towers: per micro-batch one encode of the noise-augmented first frame, a few [B]-sized torch ops and ONE
+svdx_latent_batch launch; a micro-batch is then `dict(first_frame=[B, 3, H, W], index=int64 [B])`.
+
 `examples/train_svd_amd.py` is the runnable script around this class (arguments named as in the reference, checkpoints,
 validation sampler); `bench.py` times it as `real_loop` beside the UNet-only headline."""
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Union
 
 import torch
 
 from .clip import encode_image
+from . import kernels as K
 from .train import GraphedStep, Trainer, conditioning_dropout, edm_prepare
 
 BATCH_KEYS = ("unet_in", "timesteps", "ehs", "added_time_ids", "noisy_latents", "target", "sigmas")
@@ -40,12 +45,22 @@ def rand_log_normal_reference(shape, loc: float = 0.0, scale: float = 1.0) -> to
 class TrainLoop:
     def __init__(self, trainer: Trainer, vae, image_encoder, conditioning_dropout_prob: Optional[float] = None, seed: int = 0,
                  use_graph: bool = True, ema=None, fps: int = 7, motion_bucket_id: int = 127, graph_conditioners: bool = True,
-                 reference_rng: bool = False, overlap_clip: bool = True, overlap_optimizer: bool = True):
+                 reference_rng: bool = False, overlap_clip: bool = True, overlap_optimizer: Optional[bool] = None, latent_cache=None,
+                 num_frames: Optional[int] = None):
         """reference_rng: draw cond_sigmas (:954) and sigmas (:964) the reference's way -- on the host, from the process-global generator, in
         that order -- instead of on the device from this loop's generator: a run seeded with `torch.manual_seed` then walks the reference's
         sigma sequence.  (The Gaussian noise tensors stay device draws: the reference's come from the CUDA generator, which no other device
         reproduces.)  Costs two 4-byte host-to-device copies per micro-batch."""
         self.reference_rng = reference_rng
+        # latent_cache: a LatentCache built by these towers; num_frames: the window length T (a cached micro-batch carries no clip to read it from)
+        self.cache, self.T = latent_cache, num_frames
+        if latent_cache is not None:
+            if num_frames is None or num_frames < 1 or num_frames > latent_cache.n_frames:
+                raise ValueError(f"latent_cache needs num_frames in [1, {latent_cache.n_frames}], got {num_frames}")
+            if latent_cache.device.type != trainer.dev.type or (trainer.dev.index is not None and latent_cache.device.index != trainer.dev.index):
+                raise ValueError(f"the latent cache lives on {latent_cache.device}, the trainer on {trainer.dev}")
+            latent_cache.check(vae, image_encoder, weights=False)
+            overlap_clip = False                             # no CLIP launch left to overlap
         self.tr, self.vae, self.enc = trainer, vae, image_encoder
         # overlap_clip: the CLIP embed of the first frame (~300 launches of 5-25 us on <= 150 workgroups each: latency-bound, 3.5 ms) runs on a
         # second stream BESIDE the VAE encode (chip-filling convolutions, 15.5 ms) instead of after it -- fork / join by events, also inside the
@@ -53,8 +68,9 @@ class TrainLoop:
         self.overlap_clip = overlap_clip and trainer.dev.type == "cuda"
         self._clip_stream = torch.cuda.Stream(device=trainer.dev) if self.overlap_clip else None
         # overlap_optimizer: on one rank the captured optimizer (AdamW: HBM streaming, no matrix pipe) runs on a second stream beside the next
-        # clip's conditioners instead of after them (GraphedStep.opt_beside_side_work)
-        self.overlap_optimizer = overlap_optimizer
+        # clip's conditioners instead of after them (GraphedStep.opt_beside_side_work).  None: on, except over a latent cache -- beside 1.8 ms
+        # of conditioners the fork / join costs more than it hides (+0.7 ms per iteration at 14 x 512 x 320, profiles/latent_cache.md)
+        self.overlap_optimizer = (latent_cache is None) if overlap_optimizer is None else overlap_optimizer
         self.p_drop = conditioning_dropout_prob
         self.use_graph = use_graph and trainer.dev.type == "cuda"
         self.ema = ema
@@ -131,14 +147,67 @@ class TrainLoop:
                     noisy_latents=noisy.contiguous(), target=latents.contiguous(), sigmas=sigmas)
 
     @torch.no_grad()
-    def prepare_batch(self, pixel_values: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """pixel_values [B, T, 3, H, W] in [-1, 1] (host or device) -> the step's inputs on the device (eager launches)."""
+    def _compute_cached(self, first: torch.Tensor, index: torch.Tensor, d: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """first [B, 3, H, W] float in [-1, 1] and index int64 [B] (cache row of each window's first frame) on the device + the draws ->
+        the step's inputs: `_compute` with the window's moments and the embedding read from the cache.  Capturable; `index` is read on
+        the device, so a replay serves a new window."""
+        c = self.cache
+        bsz, T = first.shape[0], self.T
+        log_normal = lambda u, loc, scale: (loc + scale * (2.0 ** 0.5) * torch.erfinv(2.0 * (u * (1 - 2e-7) + 1e-7) - 1.0)).exp()   # noqa: E731  (:63-66)
+        cond_sigmas = d["cond_sigmas"] if "cond_sigmas" in d else log_normal(d["u_cond"], -3.0, 0.5)   # :954
+        noise_aug_strength = cond_sigmas[0]                                                       # :955
+        cpix = d["n_cpix"] * cond_sigmas[:, None, None, None, None] + first[:, None]              # :957-958
+        dist_ = self.vae.encode(cpix.reshape(bsz, *cpix.shape[2:])).latent_dist                   # :959: the one frame no cache can hold
+        ehs = c.embed.index_select(0, index.clamp(0, c.n_frames - 1))                             # :975-976, computed at build time
+        sigmas = d["sigmas"] if "sigmas" in d else log_normal(d["u_sig"], 0.7, 1.6)              # :964
+        ids = torch.stack([torch.full_like(noise_aug_strength, float(self.fps)), torch.full_like(noise_aug_strength, float(self.bucket)),
+                           noise_aug_strength]).unsqueeze(0).repeat(bsz, 1)                       # :981-988
+        keep = torch.ones(bsz, 1, 1, 1, dtype=torch.float32, device=first.device)
+        if self.p_drop is not None:                                                               # :992-1011: the mask of the conditioning latent
+            ehs, keep = conditioning_dropout(d["p_drop"], ehs, keep, self.p_drop)
+        else:
+            ehs = ehs.unsqueeze(1)
+        s = sigmas.to(torch.float32)
+        den = (s ** 2 + 1) ** 0.5                                                                 # edm_prepare's divisor, per sample
+        timesteps = 0.25 * s.log()
+        zc, h, w = c.mean.shape[1:]
+        unet_in = torch.empty(bsz, T, 2 * zc, h, w, dtype=torch.float32, device=first.device)
+        noisy, target = (torch.empty(bsz, T, zc, h, w, dtype=torch.float32, device=first.device) for _ in range(2))
+        K.backend().latent_batch(c.mean, c.std, index, d["eps"], d["noise"], dist_.mean.contiguous(), dist_.std.contiguous(), s.contiguous(),
+                                 den.contiguous(), keep.reshape(bsz).contiguous(), self.vae.config.scaling_factor, unet_in, noisy, target)
+        return dict(unet_in=unet_in, timesteps=timesteps, ehs=ehs.contiguous(), added_time_ids=ids.contiguous(), noisy_latents=noisy,
+                    target=target, sigmas=sigmas)
+
+    def _cached_item(self, item) -> tuple:
+        """dict(first_frame=[B, 3, H, W], index=int64 [B]) -> the two tensors on the device.  An index still on the host is range-checked
+        here; what LatentCache.window returns always passes."""
+        if not isinstance(item, dict) or "first_frame" not in item or "index" not in item:
+            raise TypeError("a cached micro-batch is dict(first_frame=[B, 3, H, W], index=int64 [B])")
+        first, index = item["first_frame"], torch.as_tensor(item["index"])
+        m = self.cache.meta
+        if first.ndim != 4 or tuple(first.shape[1:]) != (3, m["H"], m["W"]):
+            raise ValueError(f"first_frame must be [B, 3, {m['H']}, {m['W']}] (the cache's resolution), got {tuple(first.shape)}")
+        if index.dtype != torch.int64 or index.shape != (first.shape[0],):
+            raise ValueError(f"index must be int64 [{first.shape[0]}], got {index.dtype} {tuple(index.shape)}")
+        if index.device.type == "cpu" and (int(index.min()) < 0 or int(index.max()) > self.cache.n_frames - self.T):
+            raise IndexError(f"index {index.tolist()} outside [0, {self.cache.n_frames - self.T}]")
+        return first.to(self.dev, non_blocking=True).to(torch.float32), index.to(self.dev, non_blocking=True).contiguous()
+
+    @torch.no_grad()
+    def prepare_batch(self, pixel_values) -> Dict[str, torch.Tensor]:
+        """pixel_values [B, T, 3, H, W] in [-1, 1] (host or device) -> the step's inputs on the device (eager launches).  With a latent
+        cache: dict(first_frame=[B, 3, H, W], index=int64 [B])."""
+        if self.cache is not None:
+            first, index = self._cached_item(pixel_values)
+            return self._compute_cached(first, index, self._draw(first.shape[0], self.T, first.shape[2], first.shape[3]))
         pix = pixel_values.to(self.dev, non_blocking=True).to(torch.float32)
         return self._compute(pix, self._draw(pix.shape[0], pix.shape[1], pix.shape[3], pix.shape[4]))
 
-    def _capture_conditioners(self, like: torch.Tensor) -> None:
+    def _capture_conditioners(self, like) -> None:
         """The conditioners of one micro-batch as ONE hipGraph over static inputs (pixels, draws) and outputs: ~600 eager launches of
         5-10 us of host time each become one replay (the eager form is host-bound once the UNet step itself comes from a graph)."""
+        if self.cache is not None:
+            return self._capture_cached(like)
         self._pix = torch.empty(like.shape, dtype=torch.float32, device=self.dev)
         # static draw buffers: filled per clip by _draw(into=...); zeros for the warm-up and the capture (the generator is not touched here,
         # so the captured and the eager loop consume the same random sequence)
@@ -156,10 +225,37 @@ class TrainLoop:
         torch.cuda.current_stream().wait_stream(s)
         self.cond_graph = g
 
-    def _produce(self, j: int, clip: torch.Tensor) -> None:
+    def _capture_cached(self, like) -> None:
+        """The cached form of the conditioner graph: static first frame, index and draw buffers.  The index is a device tensor the
+        captured launches read, so every replay serves the window the copy before it put there."""
+        first, index = self._cached_item(like)
+        self._first, self._index = torch.empty_like(first), torch.empty_like(index)
+        self._draws = {k: torch.zeros(v, dtype=torch.float32, device=self.dev)
+                       for k, v in self._draw_shapes(first.shape[0], self.T, first.shape[2], first.shape[3]).items()}
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._first.copy_(first)
+            self._index.copy_(index)
+            self._compute_cached(self._first, self._index, self._draws)              # warm-up on the capture stream
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=s):
+                self._cond_out = self._compute_cached(self._first, self._index, self._draws)
+        torch.cuda.current_stream().wait_stream(s)
+        self.cond_graph = g
+
+    def _produce(self, j: int, clip) -> None:
         """Micro-batch j of the NEXT step: conditioners on `clip`, result written into the tensors the captured step reads (in stream
         order this runs after the last backward sweep that read them)."""
-        if self.cond_graph is not None:
+        if self.cond_graph is not None and self.cache is not None:
+            first, index = self._cached_item(clip)
+            self._first.copy_(first)
+            self._index.copy_(index)
+            self._draw(first.shape[0], self.T, first.shape[2], first.shape[3], into=self._draws)
+            self.cond_graph.replay()
+            src = self._cond_out
+        elif self.cond_graph is not None:
             self._pix.copy_(clip.to(self.dev, non_blocking=True))
             self._draw(clip.shape[0], clip.shape[1], clip.shape[3], clip.shape[4], into=self._draws)
             self.cond_graph.replay()
@@ -171,8 +267,8 @@ class TrainLoop:
 
     # ---- the pipeline ----------------------------------------------------------------------------------------------------------
     @staticmethod
-    def _as_list(clips) -> List[torch.Tensor]:
-        return [clips] if isinstance(clips, torch.Tensor) else list(clips)
+    def _as_list(clips) -> List[Union[torch.Tensor, dict]]:
+        return [clips] if isinstance(clips, (torch.Tensor, dict)) else list(clips)
 
     def start(self, clips) -> None:
         """First clip(s) of the run: conditioners (eager), then capture of the step on the tensors they produced and of the conditioners."""

@@ -29,6 +29,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def trainable_rules(text: str):
+    """--trainable_modules -> the `trainable` of Trainer: the one rule as a string (the default stays the default), several as a tuple"""
+    rules = tuple(r.strip() for r in text.split(",") if r.strip())
+    if not rules:
+        raise ValueError("--trainable_modules: an empty list")
+    return rules[0] if len(rules) == 1 else rules
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Stable Video Diffusion fine-tuning on MI355X (svd_xtend_amd)")
     ap.add_argument("--base_folder", default=None, help="folder of per-video frame folders (train_svd.py:299); default: synthetic clips")
@@ -73,6 +81,9 @@ def parse_args(argv=None):
     ap.add_argument("--reference_rng", action="store_true",
                     help="draw cond_sigmas / sigmas the reference's way (host, process-global generator, train_svd.py:954 / :964): with --seed the run "
                          "walks the reference's sigma sequence")
+    ap.add_argument("--trainable_modules", default="temporal_transformer_block",
+                    help="comma list of what trains (svd_xtend_amd.train.select_trainable): name substrings, and @conv for every convolution "
+                         "of the UNet -- e.g. temporal_transformer_block,@conv.  Default: the reference's set (train_svd.py:761-766)")
     ap.add_argument("--latent_cache", default=None, metavar="DIR",
                     help="train from stored VAE posteriors and CLIP embeddings (svd_xtend_amd/latent_cache.py): DIR is loaded and checked against the "
                          "loaded towers when it holds a cache, otherwise one is built from every folder of --base_folder (or --cache_videos synthetic "
@@ -267,7 +278,8 @@ def main(argv=None):
     # trainable set (:758-766), AdamW (:767-773), mixed precision + DDP (:815): the Trainer
     trainer = Trainer(unet, dtype=dtype, lr=args.learning_rate, betas=(args.adam_beta1, args.adam_beta2),
                       weight_decay=args.adam_weight_decay, eps=args.adam_epsilon, grad_accum=args.gradient_accumulation_steps,
-                      max_grad_norm=args.max_grad_norm if args.clip_grad_norm else None)                  # :1045-1046
+                      max_grad_norm=args.max_grad_norm if args.clip_grad_norm else None,                  # :1045-1046
+                      trainable=trainable_rules(args.trainable_modules))
     ema_unet = None
     if args.use_ema:                                                             # :677-679
         ema_unet = EMAModel(unet.parameters(), model_cls=UNetSpatioTemporalConditionModel, model_config=unet.config,

@@ -62,7 +62,7 @@ typedef struct svdx_gather {
 
 /* ABI revision of this header: bumped whenever an entry changes its argument list or meaning (100 = rounds 1-3; 400 = round 4).
  * svdx_version() returns the value the library was built with; the ctypes binding refuses a library whose number differs. */
-#define SVDX_VERSION 612
+#define SVDX_VERSION 613
 int         svdx_version(void);
 int         svdx_last_error(char* buf, size_t n);
 /* 1 when the binary was built for gfx950 and a device is usable */
@@ -135,6 +135,36 @@ int svdx_gemm_dual(const void* A, const void* B, void* C, int M, int N, int K, i
  * GradScaler's inf check (accelerate fp16; train_svd.py:1047) done where the gradient is written; pass &opt_state[3]. */
 int svdx_gemm_tn(const void* A, const void* B, float* C, int R, int N, int K, int lda, int ldb, int ldc,
                  float* a_colsum, const void* zero_page, int out_mode, int split_k, int stages, float* found_inf, int dtype, void* stream);
+
+/* Weight gradient of a convolution: svdx_gemm_tn whose X operand is GATHERED,  C[n*ldc + k] (+)= sum_r A[r*lda + n] * Aeff[r][k],
+ * Aeff [R, taps * gather->cin] exactly the A operand svdx_gemm forms for the same `gather` (row r = output pixel, k = tap * cin + ci; a tap
+ * outside the image contributes zeros) from X, the convolution's input rows (pitch gather->lda).  Replaces the dW part of autograd's
+ * conv2d / conv3d backward (train_svd.py:1044; the reference trains every UNet parameter) without an im2col buffer.  C is [N][taps * cin]
+ * -- the GEMM layout [cout][tap][cin_p]; svdx_conv_wgrad_finalize carries it to the parameter's.  gather->mode: SVDX_GATHER_CONV3X3
+ * (stride 1 | 2, ups) or SVDX_GATHER_TEMPORAL3, any other mode is an argument error; cin % 8 == 0.  out_mode F32 / F32_ADD / F32_SLAB,
+ * a_colsum, split_k, found_inf and the XCD placement of the row slices as svdx_gemm_tn; stages 0 / 2..4 (the 128 x 128 four-wave tile).
+ * Both operands must lie below 2 GiB (argument error otherwise). */
+int svdx_gemm_tn_gather(const void* A, const void* X, float* C, int R, int N, int lda, int ldc, const svdx_gather* gather,
+                        float* a_colsum, int out_mode, int split_k, int stages, float* found_inf, int dtype, void* stream);
+
+/* The reducing launch behind svdx_gemm_tn_gather: w_grad[(n*cin + ci)*taps + tap] (+)= alpha * sum_z acc[z*slab_stride + n*ld_acc + tap*cin_p + ci]
+ * for n < cout, ci < cin -- slice 0 first (a fixed order: run-to-run identical), the padded columns ci >= cin and rows n >= cout dropped,
+ * the result in diffusers' parameter layout [cout][cin][taps] (nn.Conv2d [cout, cin, 3, 3] / nn.Conv3d [cout, cin, 3, 1, 1]).  nsplit = 1:
+ * an unsplit result.  store: 1 -> w_grad = (a gradient written once per step), 0 -> w_grad +=.  colsum_slabs (may be NULL, then b_grad too):
+ * float[nsplit][colsum_ld] left by a_colsum; b_grad[n] (+)= alpha * their sum.  alpha: the constant folded into the packed weights
+ * (svdx_conv_pack's out_scale), which the gradient of the master weight carries as a factor.  found_inf (may be NULL): see svdx_gemm_tn. */
+int svdx_conv_wgrad_finalize(const float* acc, int nsplit, int64_t slab_stride, int ld_acc, float* w_grad, int cout, int cin, int cin_p,
+                             int taps, float alpha, int store, const float* colsum_slabs, int colsum_ld, float* b_grad, float* found_inf,
+                             void* stream);
+
+/* The 16-bit operands of a convolution from its fp32 master [cout][cin][taps] (after an optimizer step, inside the captured step):
+ *   w [cout][taps][cin_p]:  w[(co*taps + tap)*cin_p + ci]  = (dtype)(master[(co*cin + ci)*taps + tap] * out_scale)           (forward)
+ *   wd [cin][taps][cout_p]: wd[(ci*taps + tap)*cout_p + co] = the same value of tap' = flip ? taps - 1 - tap : tap            (data gradient; may be NULL)
+ * one fp32 multiply, one rounding; channels ci in [cin, cin_p) of w and co in [cout, cout_p) of wd are written as zeros.  flip: the 3x3
+ * and temporal convolutions at stride 1, whose data gradient is the convolution with the reversed taps.  taps 1, 3 or 9.
+ * bias_out (float [cout], may be NULL) = bias * out_scale, the bias the forward adds beside the scaled weights (a distinct buffer). */
+int svdx_conv_pack(const float* master, float out_scale, void* w, void* wd, int cout, int cin, int taps, int cin_p, int cout_p, int flip,
+                   const float* bias, float* bias_out, int dtype, void* stream);
 
 /* Epilogue of a split-K GEMM run with SVDX_OUT_F32_SLAB: v = sum_z acc[z*slab_stride + m*N + n] + bias + rowvec + res (same operand
  * meaning as svdx_gemm); c_is_f32_accumulate: 0 -> C[m*ldc+n] = (dtype)v, 1 -> ((float*)C)[m*ldc+n] += v, 2 -> ((float*)C)[m*ldc+n] = v

@@ -37,13 +37,9 @@ struct GemmParams {
 
 struct RowInfo { int a, b, base; };   // per gathered A row (meaning depends on gather mode)
 
-template <typename T>
-__device__ __forceinline__ const T* a_row_ptr(const GemmParams& p, const RowInfo& ri, int m_clamped, int k0,
-                                              int tap, int ci0, bool& valid) {
-    const T* A = reinterpret_cast<const T*>(p.A);
-    const svdx_gather& g = p.g;
-    valid = true;
-    if (g.mode == SVDX_GATHER_PLAIN) return A + (size_t)m_clamped * p.lda + k0;
+// Source row (of the gathered tensor) that tap `tap` of a gathered A row reads; valid: the tap lies inside the image.  The one place the
+// tap -> source map is written down: the forward / data-gradient staging (a_row_ptr) and the weight-gradient staging (gemm_tn.hip) call it.
+__device__ __forceinline__ int a_row_src(const svdx_gather& g, const RowInfo& ri, int tap, bool& valid) {
     int src;
     if (g.mode == SVDX_GATHER_CONV3X3 || g.mode == SVDX_GATHER_CONV3X3_PAD0) {
         int dy = tap / 3, dx = tap - dy * 3;
@@ -61,6 +57,17 @@ __device__ __forceinline__ const T* a_row_ptr(const GemmParams& p, const RowInfo
         valid = (ts >= 0) & (ts < g.t);
         src = ri.base + ts * g.hw;
     }
+    return src;
+}
+
+template <typename T>
+__device__ __forceinline__ const T* a_row_ptr(const GemmParams& p, const RowInfo& ri, int m_clamped, int k0,
+                                              int tap, int ci0, bool& valid) {
+    const T* A = reinterpret_cast<const T*>(p.A);
+    const svdx_gather& g = p.g;
+    valid = true;
+    if (g.mode == SVDX_GATHER_PLAIN) return A + (size_t)m_clamped * p.lda + k0;
+    const int src = a_row_src(g, ri, tap, valid);
     return A + (size_t)(valid ? src : 0) * g.lda + ci0;
 }
 

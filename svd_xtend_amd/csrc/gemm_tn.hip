@@ -110,11 +110,73 @@ __device__ __forceinline__ TnSlice tn_k_slice(const GemmParams& p, int z) {
     return TnSlice{kt_begin, min(kt_total, kt_begin + kt_per)};
 }
 
+// GATHER (svdx_gemm_tn_gather, the convolution weight gradients; the template value is the gather mode, SVDX_GATHER_CONV3X3 or
+// SVDX_GATHER_TEMPORAL3, 0 = the plain kernel): byte offset into the gathered tensor p.B of the 16-byte piece that holds columns
+// k .. k + 7 (k = tap * cin + ci; a piece never straddles taps, cin % 8 == 0) of row r of Aeff -- the operand svdx_gemm's forward sees for
+// the same p.g.  The row -> source row map IS the forward's (decode_row / a_row_src of gemm_common.h).  A row >= R, a tap outside the
+// image and a column beyond taps * cin (tap < 0) get the offset beyond num_records, so the piece reads zeros.  Branch-free: the mode is
+// a compile-time constant here (a_row_src's mode tests fold away), the rest are selects.
+template <int MODE>
+__device__ __forceinline__ unsigned tn_gather_voff(const GemmParams& p, const RowInfo& ri, int r, int tap, int ci) {
+    svdx_gather g = p.g;
+    g.mode = MODE;
+    bool valid;
+    const int src = a_row_src(g, ri, tap, valid);
+    return (valid & (r < p.K) & (tap >= 0)) ? (unsigned)(src * g.lda + ci) * 2u : TN_OOB;
+}
+// decode_row costs two integer divisions, and a thread stages four rows of EVERY K-tile: decoded per tile, the address arithmetic outweighed
+// the tile's MFMAs (profiles/conv_wgrad.md).  So each thread decodes its four rows once, for its first K-tile, and WALKS them from tile to
+// tile: BK rows further on is a fixed step in (x, y, image) -- or (pixel, frame, clip) -- with at most one carry per coordinate.  Every
+// constant of the walk comes out of decode_row itself (rows 0, BK and one image), so the walk cannot drift from the forward's map; the
+// simulator runs it against the float64 convolutions at widths from 2 to 16 and clips of 1 to 14 frames.
+// In the temporal mode RowInfo::b (unused by that map) carries the pixel index, which decode_row folds into `base`.
+struct TnWalk { int db, b_wrap, b_size, da, a_carry, a_wrap, a_size, dbase, unit; };
+template <int MODE>
+__device__ __forceinline__ TnWalk tn_walk(const svdx_gather& g0) {
+    svdx_gather g = g0;
+    g.mode = MODE;
+    const RowInfo z = decode_row(g, 0), d = decode_row(g, BK);
+    TnWalk w;
+    if (MODE == SVDX_GATHER_TEMPORAL3) {
+        w.db = BK % g.hw; w.b_size = g.hw; w.b_wrap = g.hw;                                   // pixel
+        w.da = d.a - z.a; w.a_carry = 1; w.a_size = g.t; w.a_wrap = g.t;                      // frame
+        w.unit = decode_row(g, g.t * g.hw).base - z.base;                                     // one clip
+        w.dbase = d.base - z.base - w.db;                                                     // whole clips in BK rows
+    } else {
+        w.db = d.b - z.b; w.b_size = g.wo * g.stride; w.b_wrap = w.b_size + z.b;              // x (RowInfo::b = x * stride - 1)
+        w.da = d.a - z.a; w.a_carry = g.stride; w.a_size = g.ho * g.stride; w.a_wrap = w.a_size + z.a;
+        w.unit = decode_row(g, g.wo * g.ho).base - z.base;                                    // one image
+        w.dbase = d.base - z.base;
+    }
+    return w;
+}
+template <int MODE>
+__device__ __forceinline__ RowInfo tn_walk_first(const svdx_gather& g0, int r) {
+    svdx_gather g = g0;
+    g.mode = MODE;
+    RowInfo ri = decode_row(g, r);
+    if (MODE == SVDX_GATHER_TEMPORAL3) ri.b = r % g.hw;
+    return ri;
+}
+template <int MODE>
+__device__ __forceinline__ void tn_walk_step(const TnWalk& w, RowInfo& ri) {
+    ri.b += w.db;
+    const bool cb = ri.b >= w.b_wrap;
+    ri.b -= cb ? w.b_size : 0;
+    if (MODE == SVDX_GATHER_TEMPORAL3) ri.base += w.db - (cb ? w.b_size : 0);
+    ri.a += w.da + (cb ? w.a_carry : 0);
+    const bool ca = ri.a >= w.a_wrap;
+    ri.a -= ca ? w.a_size : 0;
+    ri.base += w.dbase + (ca ? w.unit : 0);
+}
+
 // BUF (round 5): the staging as buffer_load ... lds through two raw descriptors (operands below 2 GiB), issued by hidden_dma above: per-thread
 // byte offsets computed once, the row bound from num_records instead of a zero page (a column beyond the operand gets an offset beyond it), and
 // -- the point -- no compiler-inserted vmcnt(0) between the staging pieces and the fragment reads: loads and MFMAs overlap at last.
-template <typename T, int NSTG, bool BUF = false>
+// GATHER (needs BUF): B is the source tensor of p.g and the B tile is gathered from it, row by row of every K-tile (tn_gather_voff).
+template <typename T, int NSTG, bool BUF = false, int GATHER = 0>
 __global__ __launch_bounds__(NTHREADS) void gemm_tn_kernel(GemmParams p) {
+    static_assert(BUF || !GATHER, "the gathered B operand is staged through its buffer descriptor");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef typename TT<T>::v8 v8;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -140,13 +202,22 @@ __global__ __launch_bounds__(NTHREADS) void gemm_tn_kernel(GemmParams p) {
     // BUF: byte offsets of this thread's four pieces inside K-tile 0 (tn_voff; the K-tile adds kt * BK rows)
     const desc4 rsA = hidden_desc(p.A, BUF ? (unsigned)p.a_bytes : 0u), rsB = hidden_desc(p.B, BUF ? (unsigned)p.b_bytes : 0u);
     unsigned voa[4], vob[4];
+    int gtap[4], gci[4];                                 // GATHER: tap (-1: a column beyond the operand) and channel of this thread's four pieces
+    RowInfo gri[4];                                      // GATHER: this thread's four rows of the K-tile staged next (issue() walks them on)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = i * 16 + ld_row;
         const int lc = pc ^ (tn_rid(row) << 1);
         voa[i] = tn_voff(row, p.lda, m0 + lc * 8, p.M);
         vob[i] = tn_voff(row, p.ldb, n0 + lc * 8, p.N);
+        if (GATHER) {
+            const int k = n0 + lc * 8;
+            gtap[i] = k < p.N ? k / p.g.cin : -1;
+            gci[i] = k - gtap[i] * p.g.cin;
+            gri[i] = tn_walk_first<GATHER>(p.g, kt_begin * BK + row);
+        }
     }
+    const TnWalk walk = GATHER ? tn_walk<GATHER>(p.g) : TnWalk{};
     auto issue = [&](int kt, int stage) __attribute__((always_inline)) {
         char* As = smem + stage * STAGE_BYTES;
         char* Bs = As + BM * BK * 2;
@@ -157,7 +228,8 @@ __global__ __launch_bounds__(NTHREADS) void gemm_tn_kernel(GemmParams p) {
             for (int i = 0; i < 4; ++i) {
                 const int base = (i * 256 + wave_u * 64) * 16;
                 hidden_dma<16>(rsA, As + base, voa[i] + ka);
-                hidden_dma<16>(rsB, Bs + base, vob[i] + kb);
+                hidden_dma<16>(rsB, Bs + base, GATHER ? tn_gather_voff<GATHER>(p, gri[i], kt * BK + i * 16 + ld_row, gtap[i], gci[i]) : vob[i] + kb);
+                if (GATHER) tn_walk_step<GATHER>(walk, gri[i]);          // issue() is called for consecutive K-tiles
             }
             return;
         }
@@ -453,13 +525,13 @@ static long tn_arrange(GemmParams& p) {
     return 8L * p.sub_m * p.sub_n;
 }
 
-template <typename T, int NSTG, bool BUF = false>
+template <typename T, int NSTG, bool BUF = false, int GATHER = 0>
 int launch_gemm_tn(GemmParams p, hipStream_t st) {
     constexpr int LDS = NSTG * STAGE_BYTES;
-    [[maybe_unused]] static const bool lds_ok = allow_lds(&gemm_tn_kernel<T, NSTG, BUF>, LDS);
+    [[maybe_unused]] static const bool lds_ok = allow_lds(&gemm_tn_kernel<T, NSTG, BUF, GATHER>, LDS);
     dim3 grid((unsigned)tn_arrange(p));
-    hipLaunchKernelGGL((gemm_tn_kernel<T, NSTG, BUF>), grid, dim3(NTHREADS), LDS, st, p);
-    SVDX_LAUNCH_CHECK("svdx_gemm_tn");
+    hipLaunchKernelGGL((gemm_tn_kernel<T, NSTG, BUF, GATHER>), grid, dim3(NTHREADS), LDS, st, p);
+    SVDX_LAUNCH_CHECK(GATHER ? "svdx_gemm_tn_gather" : "svdx_gemm_tn");
     return 0;
 }
 
@@ -514,5 +586,55 @@ extern "C" int svdx_gemm_tn(const void* A, const void* B, float* C, int R, int N
         if (stages == 3) return buf ? launch_gemm_tn<T, 3, true>(p, st) : launch_gemm_tn<T, 3>(p, st);
         if (stages == 4) return buf ? launch_gemm_tn<T, 4, true>(p, st) : launch_gemm_tn<T, 4>(p, st);
         return buf ? launch_gemm_tn<T, 2, true>(p, st) : launch_gemm_tn<T, 2>(p, st);
+    });
+}
+
+extern "C" int svdx_gemm_tn_gather(const void* A, const void* X, float* C, int R, int N, int lda, int ldc, const svdx_gather* gather,
+                                   float* a_colsum, int out_mode, int split_k, int stages, float* found_inf, int dtype, void* stream) {
+    SVDX_CHECK_ARG(A && X && C && gather && R > 0 && N > 0, "svdx_gemm_tn_gather: bad args");
+    const svdx_gather& g = *gather;
+    SVDX_CHECK_ARG(g.mode == SVDX_GATHER_CONV3X3 || g.mode == SVDX_GATHER_TEMPORAL3,
+                   "svdx_gemm_tn_gather: gather mode %d (the 3x3 convolution and the temporal convolution only)", g.mode);
+    SVDX_CHECK_ARG(g.cin > 0 && g.cin % 8 == 0 && g.lda >= g.cin && g.lda % 8 == 0 && g.n_img > 0, "svdx_gemm_tn_gather: cin=%d lda=%d must be multiples of 8", g.cin, g.lda);
+    long src_rows;
+    if (g.mode == SVDX_GATHER_CONV3X3) {
+        SVDX_CHECK_ARG(g.stride == 1 || g.stride == 2, "svdx_gemm_tn_gather: conv stride");
+        SVDX_CHECK_ARG(g.ups == 0 || (g.ups == 1 && g.hi % 2 == 0 && g.wi % 2 == 0), "svdx_gemm_tn_gather: upsampled dims must be even");
+        SVDX_CHECK_ARG(g.hi > 0 && g.wi > 0 && g.ho > 0 && g.wo > 0 && (long)R == (long)g.n_img * g.ho * g.wo, "svdx_gemm_tn_gather: conv rows mismatch");
+        src_rows = (long)g.n_img * (g.hi >> g.ups) * (g.wi >> g.ups);
+    } else {
+        SVDX_CHECK_ARG(g.t > 0 && g.hw > 0 && (long)R == (long)g.n_img * g.t * g.hw, "svdx_gemm_tn_gather: temporal rows mismatch");
+        src_rows = R;
+    }
+    const int K = (g.mode == SVDX_GATHER_TEMPORAL3 ? 3 : 9) * g.cin;
+    SVDX_CHECK_ARG(!found_inf || out_mode == SVDX_OUT_F32 || out_mode == SVDX_OUT_F32_ADD, "svdx_gemm_tn_gather: found_inf goes with the store / += modes");
+    SVDX_CHECK_ARG(stages == 0 || (stages >= 2 && stages <= 4), "svdx_gemm_tn_gather: stages=%d (0 = default, 2..4 stages of the 128x128 tile)", stages);
+    SVDX_CHECK_ARG(out_mode == SVDX_OUT_F32 || out_mode == SVDX_OUT_F32_ADD || out_mode == SVDX_OUT_F32_SLAB, "svdx_gemm_tn_gather: F32, F32_ADD or F32_SLAB output");
+    SVDX_CHECK_ARG(split_k >= 1 && (split_k == 1 || out_mode == SVDX_OUT_F32_SLAB), "svdx_gemm_tn_gather: split_k needs slab output");
+    SVDX_CHECK_ARG(out_mode != SVDX_OUT_F32_SLAB || (split_k - 1) * cdiv(cdiv(R, BK), split_k) < cdiv(R, BK),
+                   "svdx_gemm_tn_gather: split_k=%d leaves slices without rows (R=%d): their slabs would stay unwritten", split_k, R);
+    SVDX_CHECK_ARG(N % 8 == 0 && lda >= N && lda % 8 == 0 && ldc >= K && ((uintptr_t)A & 15) == 0 && ((uintptr_t)X & 15) == 0,
+                   "svdx_gemm_tn_gather: operands must be 16-byte aligned, N and lda multiples of 8, ldc >= taps * cin");
+    // both operands go through buffer descriptors (the flat staging of svdx_gemm_tn has no gathered form): below 2 GiB only
+    const long a_span = ((long)(R - 1) * lda + N) * 2, x_span = ((src_rows - 1) * g.lda + g.cin) * 2;
+    SVDX_CHECK_ARG(a_span <= 0x7ffffff0L && x_span <= 0x7ffffff0L, "svdx_gemm_tn_gather: operands of 2 GiB and more are not supported");
+    GemmParams p{};
+    p.A = A; p.B = X; p.C = C; p.M = N; p.N = K; p.K = R; p.lda = lda; p.ldb = g.lda; p.ldc = ldc;
+    p.g = g; p.out_mode = out_mode; p.alpha = 1.f; p.split_k = split_k;
+    p.a_colsum = a_colsum; p.found_inf = found_inf;
+    p.a_bytes = (int)a_span; p.b_bytes = (int)x_span;
+    p.tiles_m = cdiv(N, BM); p.tiles_n = cdiv(K, BN);
+    p.vec_ok = (ldc % 4 == 0) && (((uintptr_t)C & 15) == 0);
+    p.slab_stride = (long)N * ldc;
+    DISPATCH_DTYPE(dtype, {
+        hipStream_t st = (hipStream_t)stream;
+        if (g.mode == SVDX_GATHER_TEMPORAL3) {
+            if (stages == 3) return launch_gemm_tn<T, 3, true, SVDX_GATHER_TEMPORAL3>(p, st);
+            if (stages == 4) return launch_gemm_tn<T, 4, true, SVDX_GATHER_TEMPORAL3>(p, st);
+            return launch_gemm_tn<T, 2, true, SVDX_GATHER_TEMPORAL3>(p, st);
+        }
+        if (stages == 3) return launch_gemm_tn<T, 3, true, SVDX_GATHER_CONV3X3>(p, st);
+        if (stages == 4) return launch_gemm_tn<T, 4, true, SVDX_GATHER_CONV3X3>(p, st);
+        return launch_gemm_tn<T, 2, true, SVDX_GATHER_CONV3X3>(p, st);
     });
 }

@@ -26,7 +26,7 @@ LN_PARTIAL_ROWS = 2048
 GN_REPLICAS = 8
 GN_STAT_FLOATS = 4             # floats of storage per (replica, sample, group) of a GroupNorm statistics buffer: two int64
 GATHER_PLAIN, GATHER_CONV3X3, GATHER_CONV3X3_DGRAD2, GATHER_TEMPORAL3, GATHER_CONV3X3_PAD0 = 0, 1, 2, 3, 4
-ABI_VERSION = 612              # include/svdx.h: SVDX_VERSION this binding was written against
+ABI_VERSION = 613              # include/svdx.h: SVDX_VERSION this binding was written against
 OPT_STATE_FLOATS = 16          # include/svdx.h: layout of the optimizer / loss-scale / schedule state
 SCHED_KINDS = {"constant": 0, "constant_with_warmup": 1, "linear": 2, "cosine": 3, "cosine_with_restarts": 4, "polynomial": 5, "piecewise_constant": 6}
 SCHED_MAX_RULES = 8            # include/svdx.h SVDX_SCHED_MAX_RULES: step rules of piecewise_constant, stored behind the 16 state floats
@@ -90,6 +90,9 @@ _SIGS = {
     "svdx_gemm_dual": "ppp" "iiiiii" "p" "piii" "pi" "pp" "ifi" "pp" "iiii" "ip",
     "svdx_gemm_gn": "ppp" "iiiiii" "p" "piii" "pi" "pp" "fi" "pii" "ip",
     "svdx_gemm_tn": "ppp" "iiiiii" "pp" "iii" "p" "ip",
+    "svdx_gemm_tn_gather": "ppp" "iiii" "pp" "iii" "p" "ip",
+    "svdx_conv_wgrad_finalize": "pil" "ip" "iiii" "fi" "pi" "pp" "p",
+    "svdx_conv_pack": "pf" "pp" "iiiii" "i" "pp" "ip",
     "svdx_gemm_finalize": "pil" "pi" "iii" "pp" "iii" "pi" "ppi" "ip",
     "svdx_gemm_finalize_gn": "pil" "p" "iii" "pp" "iii" "pi" "pii" "ip",
     "svdx_small_linear": "pppp" "iiii" "iii" "ip",
@@ -335,6 +338,26 @@ class HipBackend:
         """found_inf: one-float view (opt_state[3:4]) set to 1 when a value left in C is not finite (store / += modes)."""
         self._call("svdx_gemm_tn", _p(A), _p(B), _f32(C), R, N, K, lda, ldb, ldc, _f32(a_colsum), _p(self._zero_page), out_mode, split_k, stages,
                    _f32(found_inf), _dt(A), self._stream())
+
+    def gemm_tn_gather(self, A, X, C, R, N, lda, ldc, gather: Gather, out_mode=OUT_F32_SLAB, split_k=1, a_colsum=None, stages=0, found_inf=None):
+        """include/svdx.h svdx_gemm_tn_gather: C [N][taps * gather.cin] (+)= A[:, :N]^T Aeff, Aeff the gathered operand svdx_gemm forms from X."""
+        g = gather.to_c()
+        if self.launch_log is not None:
+            self._log_extra = [gather.mode, gather.cin, gather.stride, gather.ups]
+        self._call("svdx_gemm_tn_gather", _p(A), _p(X), _f32(C), R, N, lda, ldc, ctypes.cast(ctypes.pointer(g), ctypes.c_void_p), _f32(a_colsum),
+                   out_mode, split_k, stages, _f32(found_inf), _dt(A), self._stream())
+
+    def conv_wgrad_finalize(self, acc, nsplit, slab_stride, ld_acc, w_grad, cout, cin, cin_p, taps, alpha=1.0, store=True, colsum_slabs=None,
+                            colsum_ld=0, b_grad=None, found_inf=None):
+        """include/svdx.h svdx_conv_wgrad_finalize: the slabs [nsplit][cout..][taps * cin_p] -> w_grad [cout][cin][taps] (and b_grad), times alpha."""
+        self._call("svdx_conv_wgrad_finalize", _f32(acc), nsplit, slab_stride, ld_acc, _f32(w_grad), cout, cin, cin_p, taps, float(alpha), int(bool(store)),
+                   _f32(colsum_slabs), colsum_ld, _f32(b_grad), _f32(found_inf), self._stream())
+
+    def conv_pack(self, master, out_scale, w, wd, cout, cin, taps, cin_p, cout_p, flip, bias=None, bias_out=None):
+        """include/svdx.h svdx_conv_pack: master [cout][cin][taps] (float) -> w [cout][taps][cin_p], wd [cin][taps][cout_p] (or None);
+        bias_out (or None) = bias * out_scale."""
+        self._call("svdx_conv_pack", _f32(master), float(out_scale), _p(w), _p(wd), cout, cin, taps, cin_p, cout_p, int(bool(flip)),
+                   _f32(bias), _f32(bias_out), _dt(w), self._stream())
 
     def gemm_finalize(self, acc, nsplit, slab_stride, C, M, N, ldc, bias=None, rowvec=None, rv_ld=0, rv_rpg=0, rv_mod=0,
                       res=None, ldres=0, accumulate_f32=False, dtype=None, colsum_slabs=None, colsum_out=None, gn=None):

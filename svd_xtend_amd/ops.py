@@ -694,13 +694,26 @@ def _tn_formula(M: int, N: int, Kd: int):
         sk = _tn_slices(max(1, min(256 // t18, rtiles // 32)))
         if 180 <= t18 * sk <= 256:
             return sk, 18
-    tiles = tiles_of(128, 128)
+    return _tn_slices_128(rtiles, tiles_of(128, 128)), 2
+
+
+def _tn_slices_128(rtiles: int, tiles: int) -> int:
+    """row slices for a grid of `tiles` 128 x 128 output tiles over `rtiles` 64-row tiles (svdx_gemm_tn and svdx_gemm_tn_gather)"""
     sk = 1
     if tiles < 256 and rtiles >= 16:
         sk = max(1, min(512 // tiles, rtiles // 4, 128 if tiles <= 4 else 32))
         sk = _tn_slices(sk)
         while sk > 1 and (rtiles + sk - 1) // sk * (sk - 1) >= rtiles:
             sk = _tn_slices(sk - 1)
+    return sk
+
+
+def _tn_gather_formula(M: int, N: int, Kd: int):
+    """`_tn_formula` for svdx_gemm_tn_gather, which has the 128 x 128 four-wave tile only: where the plain kernel would take the 256 x 256
+    tile, the slice count is the 128 x 128 tile's."""
+    sk, stages = _tn_formula(M, N, Kd)
+    if stages == 18:
+        sk = _tn_slices_128((M + 63) // 64, -(-N // 128) * -(-Kd // 128))
     return sk, 2
 
 
@@ -1012,8 +1025,9 @@ class SmallLoraOp:
 # --------------------------------------------------------------------------------------------------
 class ConvOp:
     """3x3 conv2d (stride 1/2, optional nearest-x2 source), 1x1 conv2d, or Conv3d (3,1,1), all as NT GEMMs
-    whose A operand is gathered on the fly (K1-K4 of SURVEY.md 2.3).  Weights are frozen on this path
-    (train_svd.py:761-766 trains only temporal transformer blocks), so only fwd + data-grad exist."""
+    whose A operand is gathered on the fly (K1-K4 of SURVEY.md 2.3).  A trainable weight (the reference's "all parameters of unet"
+    recipe) also has `bwd_dw` -- the TN GEMM over the same gathered operand (svdx_gemm_tn_gather) and the reducing launch that carries
+    the result to the parameter's [cout][cin][tap] layout -- and `refresh`, the repack of w / wd after an optimizer step."""
 
     def __init__(self, weight: nn.Parameter, bias: Optional[nn.Parameter], kind: str, stride: int = 1,
                  ups: bool = False, cin_pad: Optional[int] = None, cout_pad: Optional[int] = None, pad0: bool = False):
@@ -1026,8 +1040,11 @@ class ConvOp:
         self.cout_p = cout_pad or self.cout     # padded channel count of the *incoming gradient* rows
         self.taps = {"3x3": 9, "1x1": 1, "t3": 3}[kind]
         self.w = self.wd = None
-        if weight.requires_grad:
-            raise NotImplementedError("conv weight-grad is outside this round's trainable set")
+        self.trainable = weight.requires_grad
+        self.w_grad = self.b_grad = None
+        self.out_scale = 1.0
+        if bias is not None and bias.requires_grad != weight.requires_grad:
+            raise NotImplementedError("a convolution trains its weight and bias together")
 
     def pack(self, rt: Runtime, need_dx: bool = True, out_scale: float = 1.0) -> None:
         """out_scale: constant folded into the packed weights, data-grad weights and bias (a frozen AlphaBlender after the conv:
@@ -1047,6 +1064,66 @@ class ConvOp:
             self.wd = rt.empty(ci, tp * self.cout_p)
             rt.k.cast_from_f32(wd.reshape(-1), self.wd, wd.numel())
         self.b = None if self.bias is None else (self.bias.data * out_scale if out_scale != 1.0 else self.bias.data)
+        self.out_scale = float(out_scale)
+        if self.trainable:
+            if self.weight.grad is None or not self.weight.grad.is_contiguous():
+                raise RuntimeError("a trainable convolution needs a contiguous .grad view of the flat gradient buffer (use Trainer)")
+            self.w_grad = self.weight.grad
+            self.b_grad = None if self.bias is None else self.bias.grad
+            rt.write_once.add(id(self.weight))          # bwd_dw's reducing launch is their only gradient producer
+            # ... and the bias gradient's, which svdx_conv_wgrad_finalize STORES on the first micro-batch.  Not a 1x1 shortcut's: it goes
+            # through gemm_tn_acc, whose column sums are always accumulated (as LinearOp's), so its bias stays among the zeroed, tested slots
+            if self.bias is not None and self.kind != "1x1":
+                rt.write_once.add(id(self.bias))
+
+    def refresh(self, rt: Runtime) -> None:
+        """w / wd (and the scaled bias) from the fp32 master after an optimizer step: one launch, bit-equal to `pack`."""
+        flip = self.kind in ("3x3", "t3") and self.stride == 1
+        scaled_b = self.bias is not None and self.out_scale != 1.0        # (out_scale == 1: self.b IS the master bias)
+        rt.k.conv_pack(self.weight.data, self.out_scale, self.w, self.wd, self.cout, self.cin, self.taps, self.cin_p, self.cout_p, flip,
+                       bias=self.bias.data if scaled_b else None, bias_out=self.b if scaled_b else None)
+
+    def bwd_dw(self, rt: Runtime, dy: torch.Tensor, x: torch.Tensor, n_img: int, h: int, w: int, T: int = 0, lddy: Optional[int] = None) -> None:
+        """weight.grad (+)= out_scale * dy^T Aeff(x), bias.grad (+)= out_scale * colsum(dy): x [rows, cin_p] the forward's input, (h, w) its
+        dims, dy [M_out, lddy] with lddy (default cout_p) >= 8.  A cout below 8 (conv_out) runs at N = cout_p and keeps the first cout rows."""
+        if not self.trainable:
+            return
+        k = rt.k
+        lddy = lddy or self.cout_p
+        N = self.cout if self.cout % 8 == 0 else min(rup(self.cout, 8), lddy)
+        store = rt.grad_overwrite
+        found = rt.found_inf if rt.fold_finite else None
+        if self.kind == "1x1":          # no gather: the plain TN GEMM; [cout][cin] is the parameter's layout already
+            if self.out_scale != 1.0 or N != self.cout or self.cin_p != self.cin:
+                raise NotImplementedError("trainable 1x1 convolution with padded channels or a folded output scale")
+            gemm_tn_acc(rt, dy, x, self.w_grad.view(self.cout, self.cin), n_img * h * w, self.cout, self.cin, lddy, self.cin_p,
+                        a_colsum=self.b_grad, write_once=True)
+            return
+        ho, wo = self.out_hw(h, w)
+        if self.kind == "t3":
+            M = n_img * T * h * w
+            g = self._gather(n_img, 0, 0, 0, 0, self.cin_p, self.cin_p, T=T, hw=h * w)
+        else:
+            M = n_img * ho * wo
+            g = self._gather(n_img, ho if self.ups else h, wo if self.ups else w, ho, wo, self.cin_p, self.cin_p)
+        Kd = self.taps * self.cin_p
+
+        def run(cfg):
+            sk, stages = cfg
+            slabs = rt.f32(sk, N, Kd)
+            cs = rt.f32(sk, N) if self.b_grad is not None else None
+            k.gemm_tn_gather(dy, x, slabs, M, N, lddy, Kd, g, out_mode=K.OUT_F32_SLAB, split_k=sk, a_colsum=cs, stages=stages)
+            k.conv_wgrad_finalize(slabs, sk, N * Kd, Kd, self.w_grad, self.cout, self.cin, self.cin_p, self.taps, alpha=self.out_scale,
+                                  store=store, colsum_slabs=cs, colsum_ld=N, b_grad=self.b_grad, found_inf=found)
+
+        rtiles = (M + 63) // 64
+        tiles = -(-N // 128) * -(-Kd // 128)
+
+        def cands():
+            return [(s, v) for v in (2, 3, 4) for s in (1, 2, 4, 8, 16, 24, 32, 40, 48, 64, 96)
+                    if s == 1 or (tiles * s <= 2048 and rtiles // s >= 2 and -(-rtiles // s) * (s - 1) < rtiles)]
+
+        tuned_call(rt, ("tn_gather", M, N, Kd, g.mode, g.stride, g.ups), cands, lambda: _tn_gather_formula(M, N, Kd), run)
 
     def _gather(self, n_img, hi, wi, ho, wo, cin, lda, T=0, hw=0, dgrad=False) -> Optional[K.Gather]:
         if self.kind == "1x1":
@@ -1162,6 +1239,13 @@ class GroupNormOp:
             rt.k.gn_stats(x, stats, n_s, rows, self.C, GN_GROUPS, prezeroed=pz)
         rt.k.gn_apply(x, stats, self.mod.weight.data, self.mod.bias.data, y, n_s, rows, self.C, GN_GROUPS, self.eps, self.silu)
         return y, stats
+
+    def reapply(self, rt: Runtime, x: torch.Tensor, stats: torch.Tensor, n_s: int, rows: int) -> torch.Tensor:
+        """The forward's output again, from x and the statistics the forward saved: one svdx_gn_apply pass, no statistics pass (the
+        input of a trainable convolution, which the forward does not keep)."""
+        y = rt.empty(n_s * rows, self.C)
+        rt.k.gn_apply(x, stats, self.mod.weight.data, self.mod.bias.data, y, n_s, rows, self.C, GN_GROUPS, self.eps, self.silu)
+        return y
 
     def bwd(self, rt: Runtime, dy, x, stats, n_s: int, rows: int, add: Optional[torch.Tensor] = None):
         """The backward statistics stay a pass of their own over (dy, x): round 4 built them into the store loop of the data-gradient GEMM that

@@ -22,13 +22,26 @@ from .unet import UNetSpatioTemporalConditionModel
 ALIGN = 64  # floats
 
 
-def select_trainable(model: torch.nn.Module, substr: str = "temporal_transformer_block") -> List[str]:
-    """train_svd.py:761-766 (names containing `temporal_transformer_block`); with LoRA adapters injected
-    (train_svd_lora.py:655-671: everything frozen, then `add_adapter`) the adapters are the trainable set."""
+DEFAULT_TRAINABLE = "temporal_transformer_block"
+
+
+def select_trainable(model: torch.nn.Module, which="temporal_transformer_block") -> List[str]:
+    """Sets `requires_grad` and returns the trainable names.  `which`: a string or a sequence of strings, each either a name substring
+    (train_svd.py:761-766: names containing `temporal_transformer_block`) or "@conv" -- the parameters of every nn.Conv2d / nn.Conv3d of
+    the UNet (the ResNet halves, the down- and upsamplers, conv_in, conv_out: half of the reference's "all parameters of unet" recipe; a
+    substring "conv" would also catch the GroupNorm conv_norm_out).  With LoRA adapters injected (train_svd_lora.py:655-671: everything
+    frozen, then `add_adapter`) the adapters are the trainable set."""
+    rules = [which] if isinstance(which, str) else list(which)
+    if not rules or not all(isinstance(r, str) and r for r in rules):
+        raise ValueError(f"trainable={which!r}: a non-empty string or a sequence of them")
     has_lora = any(".lora_" in name for name, _ in model.named_parameters())
+    conv = set()
+    if "@conv" in rules:
+        conv = {id(p) for m in model.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.Conv3d)) for p in m.parameters()}
+    subs = [r for r in rules if r != "@conv"]
     names = []
     for name, p in model.named_parameters():
-        p.requires_grad = (".lora_" in name) if has_lora else (substr in name)
+        p.requires_grad = (".lora_" in name) if has_lora else (id(p) in conv or any(r in name for r in subs))
         if p.requires_grad:
             names.append(name)
     return names
@@ -36,13 +49,17 @@ def select_trainable(model: torch.nn.Module, substr: str = "temporal_transformer
 
 def build_adam_tiles(params, offsets, wt_map, device) -> torch.Tensor:
     """Tile table of svdx_adamw_tiled: every trainable parameter is cut into <= 64 x 64 tiles of its [rows, cols] view
-    (matrices as they are, everything else as one row); weights with a transposed 16-bit twin (wt_map: id -> (offset, pitch))
+    (matrices as they are, convolution weights as 64-column rows of their flat storage, everything else as one row); weights with a transposed 16-bit twin (wt_map: id -> (offset, pitch))
     carry its location so the optimizer kernel writes it.  int32 [n_tiles, 6] = off, ld, rows, cols, wt_off, ldwt."""
     rows_out = []
     for p, off in zip(params, offsets):
         wt = wt_map.get(id(p))
         if p.ndim == 2 and (wt is not None or p.shape[1] % 4 == 0):
             R, C = p.shape
+        elif p.ndim > 2 and p.numel() % 64 == 0:
+            # a convolution weight [cout, cin, kh, kw]: elementwise work without a transposed twin, cut into full 64 x 64 tiles of its flat
+            # storage (as one row of 64-column tiles the 700 M convolution weights of the UNet took 25 ms of the step: profiles/conv_wgrad.md)
+            R, C = p.numel() // 64, 64
         else:                            # vectors, and matrices whose rows are not 16-byte multiples (a LoRA factor [out, r] with
             R, C = 1, p.numel()          # r = 1, 2, 3, ...: train_svd_lora.py accepts any --rank): one flat row, no transposed twin
         if C % 4 or off % 4:
@@ -168,8 +185,12 @@ class Trainer:
     def __init__(self, model: UNetSpatioTemporalConditionModel, dtype: torch.dtype = torch.float16,
                  lr: float = 1e-5, betas=(0.9, 0.999), weight_decay: float = 1e-2, eps: float = 1e-8,
                  init_scale: float = 65536.0, growth_interval: int = 2000, process_group=None,
-                 grad_accum: int = 1, lora_param_dtype: Optional[str] = None, max_grad_norm: Optional[float] = None):
-        """max_grad_norm: None (the default: no clipping, the reference as it ships) or the `max_norm` of accelerate's
+                 grad_accum: int = 1, lora_param_dtype: Optional[str] = None, max_grad_norm: Optional[float] = None,
+                 trainable=DEFAULT_TRAINABLE):
+        """trainable: what `select_trainable` selects -- a name substring, "@conv" (every convolution of the UNet), or a sequence of them,
+        e.g. ("temporal_transformer_block", "@conv").  With LoRA adapters present the adapters are the trainable set and any other value
+        than the default is a ValueError.
+        max_grad_norm: None (the default: no clipping, the reference as it ships) or the `max_norm` of accelerate's
         clip_grad_norm_(unet.parameters(), args.max_grad_norm) -- the call train_svd.py:1045-1046 keeps commented out.  Each optimizer step
         then takes the L2 norm of the unscaled gradient averaged over ranks and micro-batches and scales it by min(1, max_norm / (norm + 1e-6))
         on the device (svdx_grad_sumsq_spans + svdx_grad_clip_coef, include/svdx.h); `grad_norm` / `clip_coef` hold the last step's values.
@@ -197,7 +218,10 @@ class Trainer:
         dev = next(model.parameters()).device
         self.dev = dev
 
-        self.names = select_trainable(model)
+        if trainable != DEFAULT_TRAINABLE and any(".lora_" in name for name, _ in model.named_parameters()):
+            raise ValueError(f"trainable={trainable!r}: with LoRA adapters injected the adapters are the trainable set")
+        self.trainable = trainable
+        self.names = select_trainable(model, trainable)
         model._flat = flatten_trainables(model, ALIGN)
         self.params, self.offsets, off, self.p_flat, self.g_flat = model._flat
         self.n_flat = off

@@ -700,6 +700,12 @@ class _ResnetHalf(nn.Module):
         if self.time_emb_proj.weight.requires_grad:
             raise NotImplementedError("time_emb_proj is frozen on this path")
 
+    def conv_ops(self):
+        return [op for op in (self.c1, self.c2, self.sc) if op is not None]
+
+    def has_trainable(self):
+        return any(op.trainable for op in self.conv_ops())
+
     def pack(self, rt, need_dx, out_scale: float = 1.0):
         self.c1.pack(rt, need_dx)
         self.c2.pack(rt, need_dx, out_scale=out_scale)
@@ -729,15 +735,27 @@ class _ResnetHalf(nn.Module):
     def drop_saved(self):
         self.sv = None
 
-    def bwd(self, rt: Runtime, dout, g: Geom, add=None):
-        """returns dx (+ add).  The identity/1x1 shortcut gradient is folded into the last GroupNorm backward."""
+    def bwd(self, rt: Runtime, dout, g: Geom, add=None, need_dx: bool = True):
+        """returns dx (+ add).  The identity/1x1 shortcut gradient is folded into the last GroupNorm backward.  A trainable convolution
+        takes its weight gradient here; its input (a1 / a2) is not saved by the forward but re-made from the saved statistics with one
+        svdx_gn_apply pass.  need_dx False: nothing upstream trains -- the weight gradients run, the input gradient is skipped (None)."""
         x, st1, h1, st2 = self.sv
         self.sv = None
         n_s, rows = self._ns(g)
         ni = g.B if self.temporal else g.N
+        if self.c2.trainable:
+            self.c2.bwd_dw(rt, dout, self.gn2.reapply(rt, h1, st2, n_s, rows), ni, g.h, g.w, T=g.T)
+        if self.sc is not None and self.sc.trainable:
+            self.sc.bwd_dw(rt, dout, x, ni, g.h, g.w, T=g.T)
+        if not need_dx and not self.c1.trainable:
+            return None
         da2 = self.c2.bwd_dx(rt, dout, ni, g.h, g.w, T=g.T)
         dh1 = self.gn2.bwd(rt, da2, h1, st2, n_s, rows)
         del da2, h1
+        if self.c1.trainable:
+            self.c1.bwd_dw(rt, dh1, self.gn1.reapply(rt, x, st1, n_s, rows), ni, g.h, g.w, T=g.T)
+        if not need_dx:
+            return None
         da1 = self.c1.bwd_dx(rt, dh1, ni, g.h, g.w, T=g.T)
         del dh1
         if self.sc is None:
@@ -767,7 +785,10 @@ class SpatioTemporalResBlock(nn.Module):
             raise NotImplementedError("mix_factor is frozen on this path")
 
     def has_trainable(self):
-        return False
+        return self.spatial_res_block.has_trainable() or self.temporal_res_block.has_trainable()
+
+    def conv_ops(self):
+        return self.spatial_res_block.conv_ops() + self.temporal_res_block.conv_ops()
 
     def pack(self, rt):
         # AlphaBlender folded away.  The temporal half has an identity shortcut, t = s + H(s) with H ending in conv2, so
@@ -776,8 +797,10 @@ class SpatioTemporalResBlock(nn.Module):
         # d s = dout + H'^T((1-a) dout) is the temporal half's own backward on dout (scaled data-grad weights).
         assert self.temporal_res_block.conv_shortcut is None
         one_minus_a = 1.0 - float(torch.sigmoid(self.time_mixer.mix_factor.data.float()))
-        self.spatial_res_block.pack(rt, self.need_dx)
-        self.temporal_res_block.pack(rt, self.need_dx, out_scale=one_minus_a)
+        # (a block with a trainable convolution runs its backward whatever `need_dx` says: the data-gradient weights exist then)
+        need_wd = self.need_dx or self.has_trainable()
+        self.spatial_res_block.pack(rt, need_wd)
+        self.temporal_res_block.pack(rt, need_wd, out_scale=one_minus_a)
 
     def first_norm(self, g: Geom):
         return self.spatial_res_block.gn1, g.N, g.HW
@@ -793,11 +816,14 @@ class SpatioTemporalResBlock(nn.Module):
         self.temporal_res_block.drop_saved()
 
     def bwd(self, rt: Runtime, dout, g: Geom):
-        if not self.need_dx:
+        if not self.need_dx and not self.has_trainable():
             self.drop_saved()
             return None
-        ds_total = self.temporal_res_block.bwd(rt, dout, g)
-        return self.spatial_res_block.bwd(rt, ds_total, g)
+        ds_total = self.temporal_res_block.bwd(rt, dout, g, need_dx=self.need_dx or self.spatial_res_block.has_trainable())
+        if ds_total is None:
+            self.spatial_res_block.drop_saved()
+            return None
+        return self.spatial_res_block.bwd(rt, ds_total, g, need_dx=self.need_dx)
 
 
 class Downsample2D(nn.Module):
@@ -808,6 +834,7 @@ class Downsample2D(nn.Module):
 
     def build(self):
         self.op = ConvOp(self.conv.weight, self.conv.bias, "3x3", stride=2)
+        self.saved_x = None          # the forward input, kept until the backward when the convolution trains
 
     def pack(self, rt):
         self.op.pack(rt, self.need_dx)
@@ -821,6 +848,7 @@ class Upsample2D(nn.Module):
 
     def build(self):
         self.op = ConvOp(self.conv.weight, self.conv.bias, "3x3", ups=True)
+        self.saved_x = None          # the forward input, kept until the backward when the convolution trains
 
     def pack(self, rt):
         self.op.pack(rt, self.need_dx)
@@ -1089,20 +1117,24 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
         self.grads_ready_cb = None       # callable(module) invoked by backward_rows after each transformer block (gradient overlap)
         self.grads_ready_flush = True    # the callback consumes the block's gradients: run the queued skinny gradient launches first
         # which modules need an input gradient: only those executed after the first trainable parameter
-        seen = False
+        # (the first trainable parameter of any kind: a transformer block's, or a convolution's -- conv_in comes first of all)
+        seen = self.conv_in.weight.requires_grad
         skip_flags = [seen]                       # conv_in output
         for kind, m in self.steps:
             if kind in ("res", "attn", "down", "up"):
                 m.need_dx = seen
-                if kind == "attn" and m.has_trainable():
+                if m.has_trainable() if kind == "attn" else any(p.requires_grad for p in m.parameters()):
                     seen = True
             elif kind == "push":
                 skip_flags.append(seen)
         self._skip_needs_grad = skip_flags
-        self._any_trainable = seen
+        self._any_trainable = seen or self.conv_out.weight.requires_grad
+        self._sweep_needed = seen                 # False: at most conv_out trains -- its weight gradient is the whole backward pass
+        conv_params = {id(p) for mod in self.modules() if isinstance(mod, (nn.Conv2d, nn.Conv3d)) for p in mod.parameters()}
         for p_name, p in self.named_parameters():
-            if p.requires_grad and "temporal_transformer_blocks" not in p_name and ".lora_" not in p_name:
-                raise NotImplementedError(f"{p_name}: only temporal_transformer_blocks.* or LoRA adapters may be trainable this round")
+            if p.requires_grad and "temporal_transformer_blocks" not in p_name and ".lora_" not in p_name and id(p) not in conv_params:
+                raise NotImplementedError(f"{p_name}: only temporal_transformer_blocks.*, LoRA adapters or the convolutions may be trainable "
+                                          "(GroupNorm affines, mix_factor, time_emb_proj, the embeddings and the spatial transformer blocks are frozen)")
 
         self.time_embedding.build()
         self.add_embedding.build()
@@ -1128,6 +1160,9 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
         for hf in halves:
             hf.temb_slice = (hf.temb_slice[0], off)
         self._temb_total = off
+        # every convolution, for refresh_trainable (the trainable ones are re-packed after an optimizer step)
+        self._conv_ops = [self.cin_op, self.cout_op] + [op for kind, m in self.steps if kind in ("res", "down", "up")
+                                                        for op in (m.conv_ops() if kind == "res" else [m.op])]
         wcat = torch.cat([hf.time_emb_proj.weight.data for hf in halves], 0).contiguous()
         self._temb_b = torch.cat([hf.time_emb_proj.bias.data for hf in halves], 0).contiguous()
         self._temb_w = rt.empty(off, wcat.shape[1])
@@ -1143,6 +1178,9 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
         for kind, m in self.steps:
             if kind == "attn":
                 m.refresh(self.rt)
+        for op in self._conv_ops:
+            if op.trainable:
+                op.refresh(self.rt)
 
     # ---- forward / backward ---------------------------------------------------------------------------
     def forward(self, sample, timestep, encoder_hidden_states, added_time_ids, return_dict: bool = True):
@@ -1161,6 +1199,8 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
         for kind, m in self.steps:
             if kind in ("res", "attn"):
                 m.drop_saved()
+            elif kind in ("down", "up"):
+                m.saved_x = None
         self._fwd_state = None
 
     def _clear_cross_pre(self):
@@ -1250,7 +1290,7 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
             return None
         pre = consumer(-1, g)                  # the statistics handle of x, here and below
         x, _, _ = self.cin_op.fwd(rt, x0, g.N, h, w, gn=pre)
-        del x0
+        x0 = x0 if self.cin_op.trainable else None        # conv_in's weight gradient reads its input again
 
         skips: List[Tuple[torch.Tensor, Geom]] = [(x, g)]
         geoms = [g]
@@ -1267,6 +1307,8 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
                 ho, wo = m.op.out_hw(cur.h, cur.w)
                 nxt = Geom(B, T, ho, wo)
                 pre = consumer(i, nxt)
+                if m.op.trainable:
+                    m.saved_x = x
                 x, ho, wo = m.op.fwd(rt, x, cur.N, cur.h, cur.w, gn=pre)
                 cur = nxt
                 if kind == "down":
@@ -1284,7 +1326,7 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
         # 3. out: GroupNorm + SiLU + conv_out
         a, st = self.gn_out.fwd(rt, x, cur.N, cur.HW, pre=pre)
         y, _, _ = self.cout_op.fwd(rt, a, cur.N, cur.h, cur.w)
-        self._fwd_state = dict(g0=g, x_last=x, st_last=st, cat_info=cat_info)
+        self._fwd_state = dict(g0=g, x_last=x, st_last=st, cat_info=cat_info, x0=x0)
         return y
 
     def _cross_precompute(self, rt, ctx, B):
@@ -1347,6 +1389,12 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
         g0 = fs["g0"]
         B, T = g0.B, g0.T
         cur = g0
+        if self.cout_op.trainable:                # conv_out's input is re-made from the saved statistics, like a resnet half's
+            self.cout_op.bwd_dw(rt, dy, self.gn_out.reapply(rt, fs["x_last"], fs["st_last"], cur.N, cur.HW), cur.N, cur.h, cur.w)
+        if not self._sweep_needed:                # nothing below conv_out wants a gradient: no data gradient is computed at all
+            self._drop_saved()
+            rt.flush_deferred()
+            return None
         da = self.cout_op.bwd_dx(rt, dy, cur.N, cur.h, cur.w)
         dx = self.gn_out.bwd(rt, da, fs["x_last"], fs["st_last"], cur.N, cur.HW)
         del da
@@ -1385,6 +1433,12 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
                 cur = level_geoms[lvl]
                 if kind in ("res", "attn"):
                     m.drop_saved()
+                elif kind in ("down", "up"):
+                    m.saved_x = None
+                elif kind == "pop_cat":          # the sweep ended above this concatenation: its skip carries no gradient either
+                    cat_info.pop()
+                    pops_left -= 1
+                    skip_grads.append(None)
                 continue
             if kind == "res" or kind == "attn":
                 dx = m.bwd(rt, dx, cur)
@@ -1394,9 +1448,13 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
                     self.grads_ready_cb(m)          # this block's weight gradients are final: the trainer may start reducing them
             elif kind == "up":
                 low = level_geoms[lvl]
+                m.op.bwd_dw(rt, dx, m.saved_x, low.N, low.h, low.w)
+                m.saved_x = None
                 dx = m.op.bwd_dx(rt, dx, low.N, low.h, low.w) if m.need_dx else None
             elif kind == "down":
                 hi = level_geoms[lvl]
+                m.op.bwd_dw(rt, dx, m.saved_x, hi.N, hi.h, hi.w)
+                m.saved_x = None
                 dx = m.op.bwd_dx(rt, dx, hi.N, hi.h, hi.w) if m.need_dx else None
             elif kind == "pop_cat":
                 Ca, Cb = cat_info.pop()
@@ -1408,6 +1466,14 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
                 dx = da_
                 skip_grads.append(db_ if self._skip_needs_grad[skip_no] else None)
             cur = level_geoms[lvl]
-        # the conv_in skip (index 0) and conv_in itself carry no trainable parameters upstream
+        # nothing upstream of conv_in trains: its output gradient -- the sweep's dx plus the conv_in skip (index 0) -- is wanted for
+        # its own weight gradient only
+        if self.cin_op.trainable and dx is not None:
+            sg = skip_grads.pop()
+            if sg is not None:
+                tmp = rt.empty(*dx.shape)
+                k.add(dx, sg, tmp, dx.numel())
+                dx = tmp
+            self.cin_op.bwd_dw(rt, dx, fs["x0"], g0.N, g0.h, g0.w)
         rt.flush_deferred()
         return None

@@ -30,7 +30,8 @@ sys.path.insert(0, ROOT)
 
 
 def trainable_rules(text: str):
-    """--trainable_modules -> the `trainable` of Trainer: the one rule as a string (the default stays the default), several as a tuple"""
+    """--trainable_modules -> the `trainable` of Trainer: the one rule as a string (the default stays the default), several as a tuple.
+    A rule is a name substring, "@conv" (every convolution) or "@norm" (the affines of every GroupNorm)."""
     rules = tuple(r.strip() for r in text.split(",") if r.strip())
     if not rules:
         raise ValueError("--trainable_modules: an empty list")
@@ -82,8 +83,8 @@ def parse_args(argv=None):
                     help="draw cond_sigmas / sigmas the reference's way (host, process-global generator, train_svd.py:954 / :964): with --seed the run "
                          "walks the reference's sigma sequence")
     ap.add_argument("--trainable_modules", default="temporal_transformer_block",
-                    help="comma list of what trains (svd_xtend_amd.train.select_trainable): name substrings, and @conv for every convolution "
-                         "of the UNet -- e.g. temporal_transformer_block,@conv.  Default: the reference's set (train_svd.py:761-766)")
+                    help="comma list of what trains (svd_xtend_amd.train.select_trainable): name substrings, @conv for every convolution "
+                         "of the UNet and @norm for the weight and bias of every GroupNorm -- e.g. temporal_transformer_block,@conv,@norm.  Default: the reference's set (train_svd.py:761-766)")
     ap.add_argument("--latent_cache", default=None, metavar="DIR",
                     help="train from stored VAE posteriors and CLIP embeddings (svd_xtend_amd/latent_cache.py): DIR is loaded and checked against the "
                          "loaded towers when it holds a cache, otherwise one is built from every folder of --base_folder (or --cache_videos synthetic "

@@ -62,7 +62,7 @@ typedef struct svdx_gather {
 
 /* ABI revision of this header: bumped whenever an entry changes its argument list or meaning (100 = rounds 1-3; 400 = round 4).
  * svdx_version() returns the value the library was built with; the ctypes binding refuses a library whose number differs. */
-#define SVDX_VERSION 613
+#define SVDX_VERSION 614
 int         svdx_version(void);
 int         svdx_last_error(char* buf, size_t n);
 /* 1 when the binary was built for gfx950 and a device is usable */
@@ -252,6 +252,16 @@ int svdx_gn_bwd_stats(const void* dy, const void* x, const float* stats, const f
 int svdx_gn_bwd_apply(const void* dy, const void* x, const float* stats, const float* bstats,
                       const float* gamma, const float* beta, const void* add, void* dx,
                       int n_s, int rows, int C, int G, float eps, int silu, int dtype, void* stream);
+/* svdx_gn_bwd_stats for a GroupNorm whose gamma / beta train: the same bstats (same format, for svdx_gn_bwd_apply), and in the same pass
+ * over dy and x the affine gradients  dgamma[c] += sum dz*xhat,  dbeta[c] += sum dz  over every sample and row (float, accumulated into).
+ * Every workgroup leaves one row of 2*C floats (dgamma | dbeta) in `partial` (16-byte aligned, svdx_gn_bwd_blocks(n_s, rows, C, G) rows);
+ * the rows are the layout of svdx_lnred_job: with defer_reduce the caller queues {partial, dgamma, dbeta, blocks, C} for
+ * svdx_ln_param_reduce_batch, without it the reducing pass is launched here.  Fixed summation order, no float atomics: run-to-run identical.
+ * (The group sums are formed from the per-channel sums times gamma: they may differ from svdx_gn_bwd_stats' in the last bits.) */
+int svdx_gn_bwd_stats_affine(const void* dy, const void* x, const float* stats, const float* gamma, const float* beta,
+                             float* bstats, float* dgamma, float* dbeta, float* partial, int n_s, int rows, int C, int G,
+                             float eps, int silu, int prezeroed, int defer_reduce, int dtype, void* stream);
+int svdx_gn_bwd_blocks(int n_s, int rows, int C, int G);
 
 /* ---- LayerNorm over C; stats[rows,2] = (mean, rstd) ------------------------------------------------- */
 int svdx_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats,

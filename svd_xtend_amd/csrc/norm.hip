@@ -72,10 +72,16 @@ __device__ __forceinline__ void gn_load8f(const float* p, float (&o)[8]) {
 }
 
 // MODE 0: stats of x.  MODE 1: backward stats (sum dz*gamma, sum dz*gamma*xhat).
-template <typename T, int MODE>
+// AFFINE (MODE 1, trainable gamma / beta): the per-channel sums over the block's rows of dz*xhat and dz -- what the fold into the 32
+// groups discards -- also leave the block, as one row partial[n * slabs + slab][2C] (gamma half, beta half) for ln_param_reduce_kernel.
+// The accumulators then hold the UNSCALED sums and gamma is applied at the fold (a second, gamma-scaled set of 16 accumulators would
+// cost registers for nothing): the group sums of this variant round differently from the frozen one's, to the same bound.  The rpi
+// threads of a column chunk meet in LDS and are added in a fixed order: no atomics, run-to-run identical.
+template <typename T, int MODE, bool AFFINE = false>
 __global__ void gn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ stats,
                                  const float* __restrict__ gamma, const float* __restrict__ beta, float* out,
-                                 GnGeom q, float eps, int silu) {
+                                 GnGeom q, float eps, int silu, float* __restrict__ partial) {
+    static_assert(!AFFINE || MODE == 1, "the affine-gradient partials ride on the backward statistics pass");
     __shared__ unsigned long long gacc[64];
     __shared__ float sm[32 * 4];
     const int t = threadIdx.x;
@@ -136,6 +142,11 @@ __global__ void gn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ 
                             const float xv = to_f<T>(xb[u].v[e]);
                             float dz = to_f<T>(db[u].v[e]);
                             if (silu) dz *= silu_gradf_(xv * sc[e] + sh[e]);
+                            if (AFFINE) {
+                                a0[e] += dz;
+                                a1[e] += dz * ((xv - mu[e]) * rs[e]);
+                                continue;
+                            }
                             const float dzg = dz * gm[e];
                             a0[e] += dzg;
                             a1[e] += dzg * (xv - mu[e]) * rs[e];
@@ -157,6 +168,7 @@ __global__ void gn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ 
                 atomicAdd(&gacc[cur * 2 + 1], (unsigned long long)__float2ll_rn(s1 * m1));
                 cur = g; s0 = 0.f; s1 = 0.f;
             }
+            if (AFFINE) { s0 += a0[e] * gm[e]; s1 += a1[e] * gm[e]; continue; }
             s0 += a0[e]; s1 += a1[e];
         }
         atomicAdd(&gacc[cur * 2], (unsigned long long)__float2ll_rn(s0 * m0));
@@ -165,6 +177,26 @@ __global__ void gn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ 
     __syncthreads();
     if (t < 2 * q.G)
         atomicAdd(reinterpret_cast<unsigned long long*>(out) + ((size_t)(slab % SVDX_GN_REPLICAS) * q.n_s + n) * q.G * 2 + t, gacc[t]);
+    if (AFFINE) {
+        // red[ry][gamma half | beta half][C]: every thread parks its 16 sums (zeros where it had no row), then the threads add the rpi
+        // copies of four adjacent columns in row order and store them with one 16-byte write
+        extern __shared__ float red[];
+        if (worker) {
+            float* mine = red + (size_t)ry * 2 * q.C + j * 8;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { mine[e] = a1[e]; mine[q.C + e] = a0[e]; }
+        }
+        __syncthreads();
+        float* prow = partial + ((size_t)n * gridDim.y + slab) * 2 * q.C;
+        for (int i = t; i < q.C / 2; i += blockDim.x) {
+            f32x4 acc = *reinterpret_cast<const f32x4*>(red + i * 4);
+            for (int k = 1; k < q.rpi; ++k) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(red + (size_t)k * 2 * q.C + i * 4);
+                acc[0] += v[0]; acc[1] += v[1]; acc[2] += v[2]; acc[3] += v[3];
+            }
+            *reinterpret_cast<f32x4*>(prow + i * 4) = acc;
+        }
+    }
 }
 
 // MODE 0: y = act(xhat*gamma+beta).  MODE 1: dx = rstd*(dz*gamma - (s1 + xhat*s2)/cnt) (+ add).
@@ -248,7 +280,14 @@ __global__ void gn_apply_kernel(const T* __restrict__ x, const T* __restrict__ d
     }
 }
 
-int gn_geom(GnGeom& q, int n_s, int rows, int C, int G, int& threads, bool reduce = false) {
+// affine-gradient form of the backward statistics launch: every block also writes (and the reducing pass reads back) a partial row of
+// 2C floats, as many bytes as TWO rows of dy and x -- slabs of at least GN_AFFINE_MIN_SLAB rows keep that at a quarter of the operand
+// traffic.  Below GN_AFFINE_MIN_BLOCKS workgroups (the 8x5 and 16x10 levels: a few MB of operands) the launch is latency-, not
+// byte-bound and the walk over a slab's rows is what it waits for: there the slabs shrink further, down to GN_AFFINE_SMALL_SLAB rows
+// (profiles/gn_affine.md: 42 workgroups of 16 rows took 20-23 us where the frozen launch's 280 of 2 rows take 13).
+constexpr int GN_AFFINE_MIN_SLAB = 16, GN_AFFINE_SMALL_SLAB = 4, GN_AFFINE_MIN_BLOCKS = 256;
+
+int gn_geom(GnGeom& q, int n_s, int rows, int C, int G, int& threads, bool reduce = false, bool affine = false) {
     SVDX_CHECK_ARG(n_s > 0 && rows > 0 && C > 0 && G > 0 && G <= 32, "groupnorm: bad sizes");
     SVDX_CHECK_ARG(C % G == 0 && C % 8 == 0 && C / 8 <= 1024, "groupnorm: C=%d must be a multiple of 8 and of G", C);
     q.n_s = n_s; q.rows = rows; q.C = C; q.G = G; q.cg = C / G; q.cc = C / 8;
@@ -258,7 +297,10 @@ int gn_geom(GnGeom& q, int n_s, int rows, int C, int G, int& threads, bool reduc
     // >= 512 blocks; the apply kernels want >= 1024 blocks of 32 rows
     int slab = reduce ? 64 : 32;
     const long want = reduce ? 512 : 1024;
-    while (slab > 2 * q.rpi && slab > 2 && (long)n_s * ((rows + slab - 1) / slab) < want) slab >>= 1;
+    const int floor_ = affine ? GN_AFFINE_MIN_SLAB : 2;
+    while (slab > 2 * q.rpi && slab > floor_ && (long)n_s * ((rows + slab - 1) / slab) < want) slab >>= 1;
+    if (affine)
+        while (slab > 2 * q.rpi && slab > GN_AFFINE_SMALL_SLAB && (long)n_s * ((rows + slab - 1) / slab) < GN_AFFINE_MIN_BLOCKS) slab >>= 1;
     q.slab = slab;
     return 0;
 }
@@ -599,7 +641,7 @@ extern "C" int svdx_gn_stats(const void* x, float* stats, int n_s, int rows, int
     dim3 grid(n_s, cdiv(rows, q.slab));
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_reduce_kernel<T, 0>), grid, dim3(threads), 0, st, (const T*)x,
                                              (const T*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                                             (const float*)nullptr, stats, q, 0.f, 0));
+                                             (const float*)nullptr, stats, q, 0.f, 0, (float*)nullptr));
     SVDX_LAUNCH_CHECK("svdx_gn_stats");
     return 0;
 }
@@ -625,8 +667,37 @@ extern "C" int svdx_gn_bwd_stats(const void* dy, const void* x, const float* sta
     if (!prezeroed) { if (int rc = svdx_zero(bstats, sizeof(long long) * 2 * n_s * G * SVDX_GN_REPLICAS, stream)) return rc; }
     dim3 grid(n_s, cdiv(rows, q.slab));
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_reduce_kernel<T, 1>), grid, dim3(threads), 0, st, (const T*)x,
-                                             (const T*)dy, stats, gamma, beta, bstats, q, eps, silu));
+                                             (const T*)dy, stats, gamma, beta, bstats, q, eps, silu, (float*)nullptr));
     SVDX_LAUNCH_CHECK("svdx_gn_bwd_stats");
+    return 0;
+}
+
+extern "C" int svdx_gn_bwd_blocks(int n_s, int rows, int C, int G) {
+    GnGeom q; int threads;
+    if (n_s <= 0 || rows <= 0 || C <= 0 || G <= 0 || G > 32 || C % G || C % 8 || C / 8 > 1024) return 0;
+    gn_geom(q, n_s, rows, C, G, threads, true, true);
+    return n_s * cdiv(rows, q.slab);
+}
+
+extern "C" int svdx_gn_bwd_stats_affine(const void* dy, const void* x, const float* stats, const float* gamma, const float* beta,
+                                        float* bstats, float* dgamma, float* dbeta, float* partial, int n_s, int rows, int C, int G,
+                                        float eps, int silu, int prezeroed, int defer_reduce, int dtype, void* stream) {
+    GnGeom q; int threads;
+    if (int rc = gn_geom(q, n_s, rows, C, G, threads, true, true)) return rc;
+    SVDX_CHECK_ARG(dgamma && dbeta && partial, "svdx_gn_bwd_stats_affine: dgamma, dbeta and partial are required");
+    SVDX_CHECK_ARG((reinterpret_cast<uintptr_t>(partial) & 15) == 0, "svdx_gn_bwd_stats_affine: partial must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (!prezeroed) { if (int rc = svdx_zero(bstats, sizeof(long long) * 2 * n_s * G * SVDX_GN_REPLICAS, stream)) return rc; }
+    dim3 grid(n_s, cdiv(rows, q.slab));
+    const int nblk = n_s * (int)grid.y;
+    const size_t sh = sizeof(float) * 16 * threads;                  // [rpi][2][C]
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_reduce_kernel<T, 1, true>), grid, dim3(threads), sh, st, (const T*)x,
+                                             (const T*)dy, stats, gamma, beta, bstats, q, eps, silu, partial));
+    SVDX_LAUNCH_CHECK("svdx_gn_bwd_stats_affine");
+    if (!defer_reduce) {
+        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3(cdiv(2 * C, 64)), dim3(1024), 0, st, partial, nblk, C, dgamma, dbeta);
+        SVDX_LAUNCH_CHECK("svdx_gn_bwd_stats_affine(param reduce)");
+    }
     return 0;
 }
 

@@ -26,7 +26,7 @@ LN_PARTIAL_ROWS = 2048
 GN_REPLICAS = 8
 GN_STAT_FLOATS = 4             # floats of storage per (replica, sample, group) of a GroupNorm statistics buffer: two int64
 GATHER_PLAIN, GATHER_CONV3X3, GATHER_CONV3X3_DGRAD2, GATHER_TEMPORAL3, GATHER_CONV3X3_PAD0 = 0, 1, 2, 3, 4
-ABI_VERSION = 613              # include/svdx.h: SVDX_VERSION this binding was written against
+ABI_VERSION = 614              # include/svdx.h: SVDX_VERSION this binding was written against
 OPT_STATE_FLOATS = 16          # include/svdx.h: layout of the optimizer / loss-scale / schedule state
 SCHED_KINDS = {"constant": 0, "constant_with_warmup": 1, "linear": 2, "cosine": 3, "cosine_with_restarts": 4, "polynomial": 5, "piecewise_constant": 6}
 SCHED_MAX_RULES = 8            # include/svdx.h SVDX_SCHED_MAX_RULES: step rules of piecewise_constant, stored behind the 16 state floats
@@ -106,6 +106,7 @@ _SIGS = {
     "svdx_gn_apply": "ppppp" "iiii" "fi" "ip",
     "svdx_gn_bwd_stats": "pppppp" "iiii" "fi" "i" "ip",
     "svdx_gn_bwd_apply": "pppppppp" "iiii" "fi" "ip",
+    "svdx_gn_bwd_stats_affine": "ppppppppp" "iiii" "fi" "ii" "ip",
     "svdx_ln_fwd": "ppppp" "ii" "f" "ip",
     "svdx_ln_bwd": "pppppp" "f" "pppp" "iii" "ip",
     "svdx_attn_fwd": "ppppp" "iiiii" "f" "ip",
@@ -157,7 +158,7 @@ _SIGS = {
 }
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "d": ctypes.c_double, "l": ctypes.c_int64, "z": ctypes.c_size_t}
 
-EXPORTED_SYMBOLS = tuple(_SIGS) + ("svdx_wall_clock_khz", "svdx_version", "svdx_last_error", "svdx_device_ok", "svdx_tsa_pixels_per_band", "svdx_ln_bwd_blocks", "svdx_gemm_tile",
+EXPORTED_SYMBOLS = tuple(_SIGS) + ("svdx_wall_clock_khz", "svdx_version", "svdx_last_error", "svdx_device_ok", "svdx_tsa_pixels_per_band", "svdx_ln_bwd_blocks", "svdx_gn_bwd_blocks", "svdx_gemm_tile",
                                     "svdx_plan_launches", "svdx_plan_bytes")
 PARAMS_F32, PARAMS_BF16_REFERENCE = 0, 1      # include/svdx.h: param_mode of svdx_adamw / svdx_adamw_tiled
 TN_FLAT = 64                   # include/svdx.h SVDX_TN_FLAT: the staging of operands >= 2 GiB, on request (tests)
@@ -186,6 +187,21 @@ def ln_bwd_blocks(rows: int, C: int) -> int:
     return max(1, min(-(-rows // (per * (256 // lanes))), cap))
 
 
+# csrc/norm.hip: rows per workgroup the affine-gradient statistics launch does not go below -- 16, or 4 while that leaves fewer than 256 workgroups
+GN_AFFINE_MIN_SLAB, GN_AFFINE_SMALL_SLAB, GN_AFFINE_MIN_BLOCKS = 16, 4, 256
+
+
+def gn_bwd_blocks(n_s: int, rows: int, C: int, G: int = 32) -> int:
+    """include/svdx.h svdx_gn_bwd_blocks: partial rows (of 2 * C floats) svdx_gn_bwd_stats_affine leaves -- csrc/norm.hip gn_geom's slab rule."""
+    rpi = 1 if C // 8 >= 256 else 256 // (C // 8)
+    slab = 64
+    while slab > 2 * rpi and slab > GN_AFFINE_MIN_SLAB and n_s * -(-rows // slab) < 512:
+        slab >>= 1
+    while slab > 2 * rpi and slab > GN_AFFINE_SMALL_SLAB and n_s * -(-rows // slab) < GN_AFFINE_MIN_BLOCKS:
+        slab >>= 1
+    return n_s * -(-rows // slab)
+
+
 def tsa_pixels_per_band(T: int, HW: int) -> int:
     """include/svdx.h svdx_tsa_pixels_per_band: the largest divisor of HW with at most 144 band rows (0: unsupported T)."""
     if T <= 0 or T > TSA_MAX_T or HW <= 0:
@@ -207,6 +223,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.svdx_tsa_pixels_per_band.restype = ctypes.c_int
     lib.svdx_ln_bwd_blocks.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.svdx_ln_bwd_blocks.restype = ctypes.c_int
+    lib.svdx_gn_bwd_blocks.argtypes = [ctypes.c_int] * 4
+    lib.svdx_gn_bwd_blocks.restype = ctypes.c_int
     lib.svdx_gemm_tile.argtypes = [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)]
     lib.svdx_gemm_tile.restype = ctypes.c_int
     for name in ("svdx_plan_launches", "svdx_plan_bytes"):
@@ -416,6 +434,14 @@ class HipBackend:
     def gn_bwd_apply(self, dy, x, stats, bstats, gamma, beta, add, dx, n_s, rows, C, G, eps, silu):
         self._call("svdx_gn_bwd_apply", _p(dy), _p(x), _f32(stats), _f32(bstats), _f32(gamma), _f32(beta),
                    _p(add), _p(dx), n_s, rows, C, G, float(eps), int(silu), _dt(x), self._stream())
+
+    def gn_bwd_stats_affine(self, dy, x, stats, gamma, beta, bstats, dgamma, dbeta, partial, n_s, rows, C, G, eps, silu, prezeroed=0,
+                            defer_reduce=False):
+        """include/svdx.h svdx_gn_bwd_stats_affine: `gn_bwd_stats` + the affine gradients.  partial: >= gn_bwd_blocks(n_s, rows, C, G) * 2 * C
+        floats; defer_reduce: the rows wait there for `ln_param_reduce_batch` (job (partial, dgamma, dbeta, gn_bwd_blocks(...), C))."""
+        assert partial.dtype == torch.float32 and partial.numel() >= gn_bwd_blocks(n_s, rows, C, G) * 2 * C
+        self._call("svdx_gn_bwd_stats_affine", _p(dy), _p(x), _f32(stats), _f32(gamma), _f32(beta), _f32(bstats), _f32(dgamma), _f32(dbeta),
+                   _f32(partial), n_s, rows, C, G, float(eps), int(silu), int(prezeroed), int(bool(defer_reduce)), _dt(x), self._stream())
 
     def ln_fwd(self, x, gamma, beta, y, stats, rows, C, eps):
         self._call("svdx_ln_fwd", _p(x), _f32(gamma), _f32(beta), _p(y), _f32(stats), rows, C, float(eps),

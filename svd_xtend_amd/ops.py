@@ -1214,8 +1214,11 @@ class GroupNormOp:
     def __init__(self, mod: nn.GroupNorm, silu: bool):
         self.mod, self.silu = mod, silu
         self.C, self.eps = mod.num_channels, mod.eps
-        if mod.weight.requires_grad:
-            raise NotImplementedError("GroupNorm affine grads are outside this round's trainable set")
+        # gamma / beta are read as float straight from the master (a view of the flat buffer once the trainer flattened it): a trainable
+        # norm has no 16-bit copy to refresh, and `reapply` sees the optimizer's update by itself
+        self.trainable = mod.weight.requires_grad
+        if mod.bias.requires_grad != self.trainable:
+            raise NotImplementedError("a GroupNorm's weight and bias are trainable together or not at all")
 
     def want(self, rt: Runtime, n_s: int, rows: int) -> Optional[GnStats]:
         """What the GEMM that writes this norm's input gets as `gn` (ops.gemm_act) so that the statistics are there when `fwd(..., pre=)`
@@ -1247,14 +1250,28 @@ class GroupNormOp:
         rt.k.gn_apply(x, stats, self.mod.weight.data, self.mod.bias.data, y, n_s, rows, self.C, GN_GROUPS, self.eps, self.silu)
         return y
 
-    def bwd(self, rt: Runtime, dy, x, stats, n_s: int, rows: int, add: Optional[torch.Tensor] = None):
+    def bwd(self, rt: Runtime, dy, x, stats, n_s: int, rows: int, add: Optional[torch.Tensor] = None, need_dx: bool = True):
         """The backward statistics stay a pass of their own over (dy, x): round 4 built them into the store loop of the data-gradient GEMM that
         writes dy (the norm's input x read beside it) and measured the step 0.12 ms SLOWER (profiles/r4_ab_in_step.txt) -- the pass
-        reads dy and x at 3 TB/s beside nothing else, the store loop read x through a workgroup that had just finished its K-loop."""
-        dx = rt.empty(n_s * rows, self.C)
+        reads dy and x at 3 TB/s beside nothing else, the store loop read x through a workgroup that had just finished its K-loop.
+        A trainable norm takes its affine gradients from that same pass (svdx_gn_bwd_stats_affine: the per-channel sums the fold into
+        groups discards), added into weight.grad / bias.grad -- slots the step zeroes, like the LayerNorm affines'.  need_dx False (a
+        trainable norm whose input gradient nobody wants): the statistics launch alone, None is returned."""
         g, b = self.mod.weight.data, self.mod.bias.data
         bst, pz = rt.take_zeroed(K.GN_REPLICAS * n_s * GN_GROUPS * K.GN_STAT_FLOATS)
-        rt.k.gn_bwd_stats(dy, x, stats, g, b, bst, n_s, rows, self.C, GN_GROUPS, self.eps, self.silu, prezeroed=pz)
+        if self.trainable:
+            dg, db = self.mod.weight.grad, self.mod.bias.grad
+            nblk = K.gn_bwd_blocks(n_s, rows, self.C, GN_GROUPS)
+            partial = rt.f32(nblk * 2 * self.C)
+            rt.k.gn_bwd_stats_affine(dy, x, stats, g, b, bst, dg, db, partial, n_s, rows, self.C, GN_GROUPS, self.eps, self.silu, prezeroed=pz,
+                                     defer_reduce=rt.batch_small)
+            if rt.batch_small:                   # the partial rows wait for the sweep's one reducing launch (Runtime.flush_deferred)
+                rt.defer_ln_reduce((partial, dg, db, nblk, self.C))
+        else:
+            rt.k.gn_bwd_stats(dy, x, stats, g, b, bst, n_s, rows, self.C, GN_GROUPS, self.eps, self.silu, prezeroed=pz)
+        if not need_dx:
+            return None
+        dx = rt.empty(n_s * rows, self.C)
         rt.k.gn_bwd_apply(dy, x, stats, bst, g, b, add, dx, n_s, rows, self.C, GN_GROUPS, self.eps, self.silu)
         return dx
 

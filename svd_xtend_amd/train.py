@@ -29,7 +29,9 @@ def select_trainable(model: torch.nn.Module, which="temporal_transformer_block")
     """Sets `requires_grad` and returns the trainable names.  `which`: a string or a sequence of strings, each either a name substring
     (train_svd.py:761-766: names containing `temporal_transformer_block`) or "@conv" -- the parameters of every nn.Conv2d / nn.Conv3d of
     the UNet (the ResNet halves, the down- and upsamplers, conv_in, conv_out: half of the reference's "all parameters of unet" recipe; a
-    substring "conv" would also catch the GroupNorm conv_norm_out).  With LoRA adapters injected (train_svd_lora.py:655-671: everything
+    substring "conv" would also catch the GroupNorm conv_norm_out) or "@norm" -- the weight and bias of every nn.GroupNorm of the UNet (the
+    ResNet halves' norm1 / norm2, the transformer models' `norm`, conv_norm_out; a substring "norm" would also catch the LayerNorms of the
+    spatial transformer blocks, which stay frozen).  With LoRA adapters injected (train_svd_lora.py:655-671: everything
     frozen, then `add_adapter`) the adapters are the trainable set."""
     rules = [which] if isinstance(which, str) else list(which)
     if not rules or not all(isinstance(r, str) and r for r in rules):
@@ -38,7 +40,9 @@ def select_trainable(model: torch.nn.Module, which="temporal_transformer_block")
     conv = set()
     if "@conv" in rules:
         conv = {id(p) for m in model.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.Conv3d)) for p in m.parameters()}
-    subs = [r for r in rules if r != "@conv"]
+    if "@norm" in rules:
+        conv |= {id(p) for m in model.modules() if isinstance(m, torch.nn.GroupNorm) for p in m.parameters()}
+    subs = [r for r in rules if r not in ("@conv", "@norm")]
     names = []
     for name, p in model.named_parameters():
         p.requires_grad = (".lora_" in name) if has_lora else (id(p) in conv or any(r in name for r in subs))
@@ -187,8 +191,8 @@ class Trainer:
                  init_scale: float = 65536.0, growth_interval: int = 2000, process_group=None,
                  grad_accum: int = 1, lora_param_dtype: Optional[str] = None, max_grad_norm: Optional[float] = None,
                  trainable=DEFAULT_TRAINABLE):
-        """trainable: what `select_trainable` selects -- a name substring, "@conv" (every convolution of the UNet), or a sequence of them,
-        e.g. ("temporal_transformer_block", "@conv").  With LoRA adapters present the adapters are the trainable set and any other value
+        """trainable: what `select_trainable` selects -- a name substring, "@conv" (every convolution of the UNet), "@norm" (the affines of
+        every GroupNorm of the UNet), or a sequence of them, e.g. ("temporal_transformer_block", "@conv", "@norm").  With LoRA adapters present the adapters are the trainable set and any other value
         than the default is a ValueError.
         max_grad_norm: None (the default: no clipping, the reference as it ships) or the `max_norm` of accelerate's
         clip_grad_norm_(unet.parameters(), args.max_grad_norm) -- the call train_svd.py:1045-1046 keeps commented out.  Each optimizer step

@@ -571,8 +571,9 @@ class TransformerSpatioTemporalModel(nn.Module):
         for b in list(self.transformer_blocks) + list(self.temporal_transformer_blocks):
             b.build()
         for n, p in self.named_parameters():
-            if p.requires_grad and "temporal_transformer_blocks" not in n and ".lora_" not in n:
-                raise NotImplementedError(f"{n}: only temporal_transformer_blocks.* or LoRA adapters may be trainable this round")
+            if p.requires_grad and "temporal_transformer_blocks" not in n and ".lora_" not in n and not n.startswith("norm."):
+                raise NotImplementedError(f"{n}: only temporal_transformer_blocks.*, the GroupNorm `norm` or LoRA adapters may be trainable "
+                                          "(proj_in / proj_out, time_pos_embed, mix_factor and the spatial transformer blocks are frozen)")
 
     def has_trainable(self):
         return any(p.requires_grad for p in self.parameters())
@@ -648,7 +649,7 @@ class TransformerSpatioTemporalModel(nn.Module):
         nl = len(self.transformer_blocks)
         for i in reversed(range(nl)):
             blk, tblk = self.transformer_blocks[i], self.temporal_transformer_blocks[i]
-            last = (i == 0) and not self.need_dx
+            last = (i == 0) and not self.need_dx and not self.gn.trainable     # (a trainable `norm` wants d(proj_in's input))
             stop = last and not blk.trainable        # nothing trainable at or before the spatial block: the sweep ends here
             dhm = rt.empty(M, C)
             k.blend_bwd(dh, self.time_mixer.mix_factor.data, None, dhm, M * C)       # (1-a) * dout for the temporal branch
@@ -663,7 +664,8 @@ class TransformerSpatioTemporalModel(nn.Module):
             if last:
                 return None
         dxn = self.pin.bwd_dx(rt, dh, M)
-        return self.gn.bwd(rt, dxn, x, st, g.N, g.HW, add=dout)
+        # need_dx False: only this norm's own affine gradients are wanted -- the statistics launch, no svdx_gn_bwd_apply
+        return self.gn.bwd(rt, dxn, x, st, g.N, g.HW, add=dout, need_dx=self.need_dx)
 
 
 # ==================================================================================================
@@ -704,7 +706,7 @@ class _ResnetHalf(nn.Module):
         return [op for op in (self.c1, self.c2, self.sc) if op is not None]
 
     def has_trainable(self):
-        return any(op.trainable for op in self.conv_ops())
+        return any(op.trainable for op in self.conv_ops()) or self.gn1.trainable or self.gn2.trainable
 
     def pack(self, rt, need_dx, out_scale: float = 1.0):
         self.c1.pack(rt, need_dx)
@@ -738,7 +740,9 @@ class _ResnetHalf(nn.Module):
     def bwd(self, rt: Runtime, dout, g: Geom, add=None, need_dx: bool = True):
         """returns dx (+ add).  The identity/1x1 shortcut gradient is folded into the last GroupNorm backward.  A trainable convolution
         takes its weight gradient here; its input (a1 / a2) is not saved by the forward but re-made from the saved statistics with one
-        svdx_gn_apply pass.  need_dx False: nothing upstream trains -- the weight gradients run, the input gradient is skipped (None)."""
+        svdx_gn_apply pass.  need_dx False: nothing upstream trains -- the weight gradients run, the input gradient is skipped (None).
+        The sweep through the block ends where nothing at or before that point trains: norm2's affines want d(a2), conv1's weights
+        d(h1), norm1's affines d(a1) (and with it d(h1)) -- whether or not an input gradient is returned."""
         x, st1, h1, st2 = self.sv
         self.sv = None
         n_s, rows = self._ns(g)
@@ -747,17 +751,22 @@ class _ResnetHalf(nn.Module):
             self.c2.bwd_dw(rt, dout, self.gn2.reapply(rt, h1, st2, n_s, rows), ni, g.h, g.w, T=g.T)
         if self.sc is not None and self.sc.trainable:
             self.sc.bwd_dw(rt, dout, x, ni, g.h, g.w, T=g.T)
-        if not need_dx and not self.c1.trainable:
+        want_dh1 = need_dx or self.c1.trainable or self.gn1.trainable
+        if not want_dh1 and not self.gn2.trainable:
             return None
         da2 = self.c2.bwd_dx(rt, dout, ni, g.h, g.w, T=g.T)
-        dh1 = self.gn2.bwd(rt, da2, h1, st2, n_s, rows)
+        dh1 = self.gn2.bwd(rt, da2, h1, st2, n_s, rows, need_dx=want_dh1)
         del da2, h1
+        if dh1 is None:
+            return None
         if self.c1.trainable:
             self.c1.bwd_dw(rt, dh1, self.gn1.reapply(rt, x, st1, n_s, rows), ni, g.h, g.w, T=g.T)
-        if not need_dx:
+        if not need_dx and not self.gn1.trainable:
             return None
         da1 = self.c1.bwd_dx(rt, dh1, ni, g.h, g.w, T=g.T)
         del dh1
+        if not need_dx:                          # norm1's affine gradients alone: the statistics launch, no input gradient
+            return self.gn1.bwd(rt, da1, x, st1, n_s, rows, need_dx=False)
         if self.sc is None:
             dsc = dout
         else:
@@ -1128,13 +1137,15 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
             elif kind == "push":
                 skip_flags.append(seen)
         self._skip_needs_grad = skip_flags
-        self._any_trainable = seen or self.conv_out.weight.requires_grad
-        self._sweep_needed = seen                 # False: at most conv_out trains -- its weight gradient is the whole backward pass
-        conv_params = {id(p) for mod in self.modules() if isinstance(mod, (nn.Conv2d, nn.Conv3d)) for p in mod.parameters()}
+        self._any_trainable = seen or self.conv_out.weight.requires_grad or self.conv_norm_out.weight.requires_grad
+        # False: at most conv_out / conv_norm_out train -- conv_out's weight gradient, and for the norm conv_out's data gradient and one
+        # statistics launch, are the whole backward pass
+        self._sweep_needed = seen
+        conv_norm_params = {id(p) for mod in self.modules() if isinstance(mod, (nn.Conv2d, nn.Conv3d, nn.GroupNorm)) for p in mod.parameters()}
         for p_name, p in self.named_parameters():
-            if p.requires_grad and "temporal_transformer_blocks" not in p_name and ".lora_" not in p_name and id(p) not in conv_params:
-                raise NotImplementedError(f"{p_name}: only temporal_transformer_blocks.*, LoRA adapters or the convolutions may be trainable "
-                                          "(GroupNorm affines, mix_factor, time_emb_proj, the embeddings and the spatial transformer blocks are frozen)")
+            if p.requires_grad and "temporal_transformer_blocks" not in p_name and ".lora_" not in p_name and id(p) not in conv_norm_params:
+                raise NotImplementedError(f"{p_name}: only temporal_transformer_blocks.*, LoRA adapters, the convolutions or the GroupNorm affines "
+                                          "may be trainable (mix_factor, time_emb_proj, the embeddings and the spatial transformer blocks are frozen)")
 
         self.time_embedding.build()
         self.add_embedding.build()
@@ -1391,7 +1402,10 @@ class UNetSpatioTemporalConditionModel(PretrainedMixin, nn.Module):
         cur = g0
         if self.cout_op.trainable:                # conv_out's input is re-made from the saved statistics, like a resnet half's
             self.cout_op.bwd_dw(rt, dy, self.gn_out.reapply(rt, fs["x_last"], fs["st_last"], cur.N, cur.HW), cur.N, cur.h, cur.w)
-        if not self._sweep_needed:                # nothing below conv_out wants a gradient: no data gradient is computed at all
+        if not self._sweep_needed:                # nothing below conv_out wants a gradient ...
+            if self.gn_out.trainable:             # ... but conv_norm_out's own affines: conv_out's data gradient and one statistics launch
+                da = self.cout_op.bwd_dx(rt, dy, cur.N, cur.h, cur.w)
+                self.gn_out.bwd(rt, da, fs["x_last"], fs["st_last"], cur.N, cur.HW, need_dx=False)
             self._drop_saved()
             rt.flush_deferred()
             return None

@@ -1,0 +1,280 @@
+"""CPU (`-m "not gpu"`): the GroupNorm affine gradients -- svdx_gn_bwd_stats_affine with the kernel source executed by the simulator of
+tests/sim/ and with the emulation of tests/gn_affine_checks.py, against float64 autograd through F.group_norm (+ F.silu) under the
+per-channel bound of gn_affine_checks.bounds; the "@norm" selection rule; one optimizer step of the tiny topology on the emulation
+against the CPU oracle; the launch audit; the planted non-finite gradient."""
+import os
+import sys
+
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "sim"))
+
+import conv_wgrad_checks as cw  # noqa: E402
+import gn_affine_checks as ga  # noqa: E402
+from svd_xtend_amd import kernels as K  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def sim():
+    from backend import SimBackend
+    return SimBackend()
+
+
+@pytest.fixture
+def emu_installed():
+    prev = K._backend
+    be = ga.GnAffineEmuBackend()
+    K._set_backend_for_tests(be)
+    yield be
+    K._set_backend_for_tests(prev)
+
+
+def test_case_table_and_block_count(sim):
+    """the issue's nine cases (+ one), and kernels.gn_bwd_blocks == svdx_gn_bwd_blocks: the host sizes `partial` as the launch writes it"""
+    assert [tuple(c) for c in ga.CASES[:9]] == [(3, 15, 64), (1, 1, 64), (2, 70, 320), (1, 210, 64), (2, 129, 640), (2, 40, 960), (2, 33, 1280),
+                                                 (1, 9, 2560), (1, 520, 320)]
+    shapes = [tuple(c) for c in ga.CASES] + [(14, 2560, 320), (14, 40, 1280), (1, 35840, 320), (14, 640, 2560), (1, 14 * 160, 1280), (25, 9216, 320)]
+    for n_s, rows, C in shapes:
+        assert K.gn_bwd_blocks(n_s, rows, C, 32) == sim.lib.svdx_gn_bwd_blocks(n_s, rows, C, 32) > 0, (n_s, rows, C)
+    assert K.gn_bwd_blocks(129, 2, 320) > 128 and sim.lib.svdx_gn_bwd_blocks(2, 8, 100, 32) == 0
+
+
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+@pytest.mark.parametrize("name", [c.name for c in ga.CASES])
+def test_kernel_case_on_simulator(sim, name, dt):
+    ga.sweep_case(sim, "cpu", ga.BY_NAME[name], ga.DT[dt])
+
+
+@pytest.mark.parametrize("name", [c.name for c in ga.CASES])
+def test_emulation_meets_the_same_reference(name):
+    """SELF-CHECK of the test double: the emulation the step tests run on meets the float64 reference under the same bound"""
+    ga.sweep_case(ga.GnAffineEmuBackend(), "cpu", ga.BY_NAME[name], torch.float16)
+
+
+def test_zeros_or_a_dropped_sample_cannot_pass():
+    """SELF-CHECK of the bound (no library code runs): all zeros, and the reference of the first sample alone, miss it almost everywhere"""
+    c = ga.BY_NAME["2x70x320"]
+    R = ga.case_reference(c, torch.float16, 1, 1e-5)
+    vg, bg, vb, bb = ga.bounds(c, R["ref"])
+    assert float((ga._ratio(torch.zeros(c.C), vg, bg) > 1).double().mean()) >= 0.95
+    assert float((ga._ratio(torch.zeros(c.C), vb, bb) > 1).double().mean()) >= 0.95
+    one = ga.Case(1, c.rows, c.C)
+    half = ga.reference(one, R["x"][:c.rows], R["dy"][:c.rows], R["gamma"], R["beta"], 1, 1e-5)
+    assert float((ga._ratio(half["dg"].float(), vg, bg) > 1).double().mean()) >= 0.95
+
+
+def test_argument_errors(sim):
+    c = ga.BY_NAME["3x15x64"]
+    R = ga.case_reference(c, torch.float16, 0, 1e-5)
+    dg, db, bst = torch.zeros(c.C), torch.zeros(c.C), torch.zeros(R["stats"].numel())
+    part = torch.zeros(K.gn_bwd_blocks(*c) * 2 * c.C + 4)
+    with pytest.raises(K.SvdxError, match="required"):
+        sim._call("svdx_gn_bwd_stats_affine", R["dy"].data_ptr(), R["x"].data_ptr(), R["stats"].data_ptr(), R["gamma"].data_ptr(), R["beta"].data_ptr(),
+                  bst.data_ptr(), dg.data_ptr(), None, part.data_ptr(), c.n_s, c.rows, c.C, 32, 1e-5, 0, 0, 0, K.F16, None)
+    with pytest.raises(K.SvdxError, match="16-byte"):
+        sim.gn_bwd_stats_affine(R["dy"], R["x"], R["stats"], R["gamma"], R["beta"], bst, dg, db, part[1:], c.n_s, c.rows, c.C, 32, 1e-5, 0)
+    with pytest.raises(AssertionError):
+        sim.gn_bwd_stats_affine(R["dy"], R["x"], R["stats"], R["gamma"], R["beta"], bst, dg, db, part[:64], c.n_s, c.rows, c.C, 32, 1e-5, 0)
+    assert not dg.any() and not db.any()
+
+
+# ---- the selection rule ---------------------------------------------------------------------------------------------------------------
+def _tiny():
+    from oracle.unet import TINY_CONFIG
+    from svd_xtend_amd.unet import UNetSpatioTemporalConditionModel
+    return UNetSpatioTemporalConditionModel(**TINY_CONFIG)
+
+
+def test_norm_rule_selects_every_groupnorm_and_nothing_else():
+    from svd_xtend_amd.train import select_trainable
+    m = _tiny()
+    gn = ga.gn_names(m)
+    assert len(gn) == 210                                  # 105 modules: 88 in the 22 ResNet pairs, 16 transformer `norm`s, conv_norm_out
+    assert sorted(select_trainable(m, "@norm")) == gn
+    assert sum(".norm1." in n or ".norm2." in n for n in gn) == 176 and sum(n.endswith(".norm.weight") for n in gn) == 16
+    # a substring "norm" is something else: it also catches the LayerNorms of the (frozen) spatial transformer blocks
+    assert len(select_trainable(_tiny(), "norm")) > 210
+    both = select_trainable(_tiny(), ("temporal_transformer_block", "@norm"))
+    assert set(gn) < set(both) and all(n in gn or "temporal_transformer_block" in n for n in both)
+    three = select_trainable(_tiny(), ["@norm", "@conv", "temporal_transformer_block"])
+    assert set(three) == set(both) | set(select_trainable(_tiny(), "@conv"))
+
+
+def test_full_topology_has_105_groupnorms():
+    """the UNet of stable-video-diffusion-img2vid as the library builds it by default, on `meta`: 105 nn.GroupNorm, 210 tensors"""
+    from svd_xtend_amd.train import select_trainable
+    from svd_xtend_amd.unet import UNetSpatioTemporalConditionModel
+    with torch.device("meta"):
+        m = UNetSpatioTemporalConditionModel()
+    assert sum(isinstance(mod, torch.nn.GroupNorm) for mod in m.modules()) == 105
+    assert len(select_trainable(m, "@norm")) == 210
+
+
+def test_norm_rule_is_ignored_under_lora_and_other_names_are_still_refused(emu_installed):
+    from svd_xtend_amd.lora import LoraConfig
+    from svd_xtend_amd.train import Trainer, select_trainable
+    lm = _tiny()
+    lm.add_adapter(LoraConfig(r=4, lora_alpha=4, init_lora_weights="gaussian"))
+    names = select_trainable(lm, "@norm")
+    assert names and all(".lora_" in n for n in names)
+    with pytest.raises(ValueError, match="LoRA"):
+        Trainer(lm, dtype=torch.float16, trainable="@norm")
+    for which, pat in (("mix_factor", "mix_factor"), ("time_emb_proj", "time_emb_proj"),
+                       ("down_blocks.0.attentions.0.transformer_blocks.0.attn1", r"transformer_blocks\.0\.attn1"),
+                       ("time_embedding", "time_embedding"), ("proj_in", "proj_in")):
+        with pytest.raises(NotImplementedError, match=pat):
+            Trainer(_tiny(), dtype=torch.float16, trainable=which)
+    m = _tiny()
+    select_trainable(m, "conv_norm_out.weight")                # a norm's weight without its bias
+    with pytest.raises(NotImplementedError, match="together"):
+        m.prepare(torch.float16)
+
+
+# ---- the step: Trainer(trainable=...) on the emulation against the CPU oracle ------------------------------------------------------------
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+@pytest.mark.parametrize("which", ga.SELECTIONS, ids=lambda w: w if isinstance(w, str) else "+".join(w))
+def test_step_matches_oracle(emu_installed, which, dt):
+    ref = ga.oracle_step(which)
+    got = cw.product_step(ref, which, ga.DT[dt], torch.device("cpu"))
+    print(ga.assert_step_parity(f"emulation {which} {dt}", ref, got, bf16=dt == "bf16"))
+    m = got["trainer"].model
+    if which == "conv_norm_out":
+        assert ref["names"] == ["conv_norm_out.bias", "conv_norm_out.weight"] and m._any_trainable and not m._sweep_needed
+        assert all(mod.sv is None for kind, blk in m.steps if kind == "res" for mod in (blk.spatial_res_block, blk.temporal_res_block))
+    else:
+        assert len([n for n in ref["names"] if n in set(ga.gn_names(m))]) == 210
+        assert all(mod.need_dx for kind, mod in m.steps[1:] if kind in ("res", "attn", "down", "up"))
+
+
+def test_conv_norm_out_alone_runs_one_data_gradient_and_one_statistics_launch(emu_installed):
+    ref = ga.oracle_step("conv_norm_out")
+    tr = cw.make_trainer(ref, "conv_norm_out", torch.float16, torch.device("cpu"))
+    tr.zero_grad()
+    emu_installed.log = log = []
+    tr.forward_backward(**cw.step_batch(ref, "cpu"))
+    emu_installed.log = None
+    i = max(j for j, e in enumerate(log) if e == "svdx_edm_loss")
+    bwd = [e for e in log[i + 1:] if e not in ("svdx_zero", "svdx_nchw_to_rows")]
+    assert bwd == ["svdx_gemm", "svdx_gn_bwd_stats_affine", "svdx_ln_param_reduce_batch"], bwd
+
+
+@pytest.mark.parametrize("which", ["up_blocks.3.resnets.2.temporal_res_block.norm2", "up_blocks.3.resnets.2.spatial_res_block.norm1",
+                                   "up_blocks.3.attentions.2.norm."])
+def test_a_trainable_tail_norm_stops_the_sweep_where_nothing_trains(emu_installed, which):
+    """need_dx == False corners: only one norm near the end of the UNet trains.  Its gradient matches the oracle; no svdx_gn_bwd_apply
+    runs for it (statistics only), and the sweep computes nothing upstream of it."""
+    import e2e_checks
+    ref = ga.oracle_step(which)
+    assert len(ref["names"]) == 2
+    emu_installed.log = log = []
+    got = cw.product_step(ref, which, torch.float16, torch.device("cpu"))
+    emu_installed.log = None
+    for n in ref["names"]:
+        assert e2e_checks.cosine(got["grads"][n], ref["grads"][n]) >= 0.9995, n
+    m = got["trainer"].model
+    upto = [mod for kind, mod in m.steps if kind in ("res", "attn", "down", "up")]
+    assert not any(mod.need_dx for mod in upto[:-1]) and not any(m._skip_needs_grad)
+    # conv_norm_out's backward (frozen: statistics + apply) and then the tail: exactly one affine launch, and its norm applies nothing
+    assert log.count("svdx_gn_bwd_stats_affine") == 1
+    i = log.index("svdx_gn_bwd_stats_affine")
+    assert log[i:i + 2] == ["svdx_gn_bwd_stats_affine", "svdx_ln_param_reduce_batch"], log[i:i + 4]      # the sweep's flush: nothing between
+
+
+def test_two_sweeps_after_zero_grad_give_the_same_gradients(emu_installed):
+    ref = ga.oracle_step(ga.ALL_THREE)
+    tr = cw.make_trainer(ref, ga.ALL_THREE, torch.float16, torch.device("cpu"))
+    batch = cw.step_batch(ref, "cpu")
+    sweeps = []
+    for _ in range(2):
+        tr.zero_grad()
+        tr.forward_backward(**batch)
+        tr.micro = 0
+        sweeps.append({n: p.grad.detach().clone() for n, p in tr.model.named_parameters() if p.requires_grad})
+    differ = [n for n in sweeps[0] if not torch.equal(sweeps[0][n], sweeps[1][n])]
+    assert not differ, differ[:8]
+    gn = set(ga.gn_names(tr.model))
+    # the affine slots are accumulated into (zeroed by the step, tested by svdx_check_finite_spans), never stored
+    assert all(id(p) not in tr.rt.write_once for n, p in tr.model.named_parameters() if n in gn)
+    spans = tr.finite_spans.tolist()
+    for p, off in zip(tr.params, tr.offsets):
+        if any(p is q for n, q in tr.model.named_parameters() if n in gn):
+            assert any(lo <= off and off + p.numel() <= lo + n for lo, n in spans)
+
+
+# ---- launch audit -----------------------------------------------------------------------------------------------------------------------
+def _step_launches(be, which):
+    ref = ga.oracle_step(ga.TEMPORAL_NORM)
+    tr = cw.make_trainer(ref, which, torch.float16, torch.device("cpu"))
+    be.log = log = []
+    tr.step(cw.step_batch(ref, "cpu"))
+    be.log = None
+    return log, tr
+
+
+def test_launch_audit(emu_installed):
+    """default set: no affine launch, the statistics launches as they were; with "@norm" every backward statistics launch has become the
+    affine entry, one per GroupNorm module, and the reducing launch is still called once per sweep (its table grows, and the entry
+    splits a table at SVDX_BATCH_MAX_JOBS jobs by itself)"""
+    import collections
+    base, _ = _step_launches(emu_installed, "temporal_transformer_block")
+    norm, tr = _step_launches(emu_installed, ga.TEMPORAL_NORM)
+    cb, cn = collections.Counter(base), collections.Counter(norm)
+    assert cb["svdx_gn_bwd_stats_affine"] == 0 and cb["svdx_gn_bwd_stats"] > 0
+    n_gn = sum(isinstance(m, torch.nn.GroupNorm) for m in tr.model.modules())
+    assert cn["svdx_gn_bwd_stats"] == 0 and cn["svdx_gn_bwd_stats_affine"] == n_gn == 105
+    # the default sweep stops at the first temporal block: with the norms trainable it goes on to the first ResNet's norm1
+    assert cb["svdx_gn_bwd_stats"] < 105 and cn["svdx_gn_stats"] == cb["svdx_gn_stats"] and cn["svdx_gn_apply"] == cb["svdx_gn_apply"]
+    assert cn["svdx_ln_param_reduce_batch"] == cb["svdx_ln_param_reduce_batch"] == 1
+    # everything else "@norm" adds is the longer sweep (the data gradients of the first down block's head), no new kind of launch
+    assert set(cn) - set(cb) == {"svdx_gn_bwd_stats_affine"}
+
+
+def test_default_set_issues_the_parents_launches(emu_installed):
+    """the default trainable set: the entry names of a step, in order, are a fixed list whose digest was recorded on the parent commit
+    with this same emulation wrapper"""
+    base, _ = _step_launches(emu_installed, "temporal_transformer_block")
+    again, _ = _step_launches(emu_installed, "temporal_transformer_block")
+    assert base == again and "svdx_gn_bwd_stats_affine" not in base
+    import hashlib
+    assert (len(base), hashlib.sha256("\n".join(base).encode()).hexdigest()) == ga.PARENT_DEFAULT_LAUNCHES, (len(base),)
+
+
+# ---- non-finite gradient ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", [ga.TEMPORAL_NORM, "@norm"], ids=["temporal+norm", "norm"])
+def test_planted_nonfinite_norm_gradient_skips_the_step(emu_installed, monkeypatch, which):
+    """one inf in the dy of one norm's backward: the step is skipped and masters and moments keep every bit -- with write-once gradients
+    beside the norms (svdx_check_finite_spans over the accumulated slots) and with the norms alone (the full pass)"""
+    from svd_xtend_amd import ops
+    ref = ga.oracle_step(which)
+    tr = cw.make_trainer(ref, which, torch.float16, torch.device("cpu"))
+    target = tr.model.mid_block.resnets[0].temporal_res_block.gn2
+    before = dict(p=tr.p_flat.clone(), m=tr.m_flat.clone(), v=tr.v_flat.clone())
+    bwd, hit = ops.GroupNormOp.bwd, []
+
+    def planted(self, rt, dy, x, *a, **k):
+        if self is target:
+            dy = dy.clone()
+            dy[3, 5] = float("inf")
+            hit.append(1)
+        return bwd(self, rt, dy, x, *a, **k)
+    monkeypatch.setattr(ops.GroupNormOp, "bwd", planted)
+    tr.step(cw.step_batch(ref, "cpu"))
+    assert hit and float(tr.opt_state[7]) == 1.0 and float(tr.opt_state[0]) == 0.0
+    assert not torch.isfinite(tr.model.mid_block.resnets[0].temporal_res_block.norm2.weight.grad).all()
+    assert torch.equal(tr.p_flat, before["p"]) and torch.equal(tr.m_flat, before["m"]) and torch.equal(tr.v_flat, before["v"])
+    monkeypatch.setattr(ops.GroupNormOp, "bwd", bwd)
+    tr.step(cw.step_batch(ref, "cpu"))                                      # the next, clean step is taken (at the halved loss scale)
+    assert float(tr.opt_state[7]) == 0.0 and float(tr.opt_state[0]) == 1.0 and not torch.equal(tr.p_flat, before["p"])
+
+
+def test_updated_affines_reach_the_next_forward(emu_installed):
+    """gamma / beta are read from the master: after an optimizer step the forward (and `reapply`, the re-made conv inputs) sees the new
+    values with nothing to refresh -- pred_after of assert_parity covers the forward; here the master IS the flat buffer"""
+    ref = ga.oracle_step("@norm")
+    tr = cw.make_trainer(ref, "@norm", torch.float16, torch.device("cpu"))
+    for p, off in zip(tr.params, tr.offsets):
+        assert p.data.data_ptr() == tr.p_flat[off:].data_ptr()
+    op = tr.model.mid_block.resnets[0].spatial_res_block.gn1
+    assert op.trainable and op.mod.weight.data.data_ptr() == tr.model.mid_block.resnets[0].spatial_res_block.norm1.weight.data.data_ptr()

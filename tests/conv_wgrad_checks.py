@@ -1,13 +1,14 @@
 """Shared checks of the convolution weight gradient (svdx_gemm_tn_gather, svdx_conv_wgrad_finalize, svdx_conv_pack): the kernel cases,
-their float64 reference (autograd through the float64 convolutions of tests/ref64.py), the error bound, the emulation backend, and the
-runners the simulator (tests/test_conv_wgrad.py) and the device (tests/test_conv_wgrad_gpu.py) both use.  TEST INFRASTRUCTURE."""
+their float64 reference (autograd through the float64 convolutions of tests/ref64.py), the error bound, and the runners the simulator
+(tests/test_conv_wgrad.py) and the device (tests/test_conv_wgrad_gpu.py) both use.  The emulation of the three entries is
+emul.EmuBackend's; the step against the oracle is selection_checks.py's.  TEST INFRASTRUCTURE."""
 from typing import NamedTuple
 
 import torch
 
-import emul
 import ref64
 from census import _ratio, ulp_of
+from selection_checks import COS_BAR
 from svd_xtend_amd import kernels as K
 
 SENTINEL = 77.0                  # exact in fp16, bf16 and fp32
@@ -251,135 +252,8 @@ def run_pack(dev, dt: torch.dtype, shape, out_scale: float, need_dx: bool = True
     assert torch.equal(master.cpu().view(-1), flats["master"].cpu()[GUARD:-GUARD])
 
 
-# ---- the emulation of the three entries -----------------------------------------------------------------------------------------------
-class ConvWgradEmuBackend(emul.EmuBackend):
-    """emul.EmuBackend + the entries the trainable convolutions add."""
-
-    def gemm_tn_gather(self, A, X, C, R, N, lda, ldc, gather, out_mode=K.OUT_F32_SLAB, split_k=1, a_colsum=None, stages=0, found_inf=None):
-        Kd = (3 if gather.mode == K.GATHER_TEMPORAL3 else 9) * gather.cin
-        assert gather.mode in (K.GATHER_CONV3X3, K.GATHER_TEMPORAL3) and gather.cin % 8 == 0
-        aeff = emul.gather_rows(X, gather, R).to(A.dtype).contiguous()
-        self.gemm_tn(A, aeff, C, R, N, Kd, lda, Kd, ldc, out_mode=out_mode, split_k=split_k, a_colsum=a_colsum, stages=stages, found_inf=found_inf)
-
-    def conv_wgrad_finalize(self, acc, nsplit, slab_stride, ld_acc, w_grad, cout, cin, cin_p, taps, alpha=1.0, store=True, colsum_slabs=None,
-                            colsum_ld=0, b_grad=None, found_inf=None):
-        v = torch.zeros(cout, taps, cin, device=acc.device)
-        for z in range(nsplit):
-            sl = torch.as_strided(acc, (cout, ld_acc), (ld_acc, 1), acc.storage_offset() + z * slab_stride)
-            v = v + sl[:, :taps * cin_p].reshape(cout, taps, cin_p)[:, :, :cin]
-        v = (v * alpha).permute(0, 2, 1).reshape(-1)
-        wg = emul.V1(w_grad, cout * cin * taps)
-        wg.copy_(v) if store else wg.add_(v)
-        bad = not torch.isfinite(wg).all()
-        if b_grad is not None:
-            s = torch.zeros(cout, device=acc.device)
-            for z in range(nsplit):
-                s = s + emul.V1(colsum_slabs, nsplit * colsum_ld)[z * colsum_ld:z * colsum_ld + cout]
-            bg = emul.V1(b_grad, cout)
-            bg.copy_(s * alpha) if store else bg.add_(s * alpha)
-            bad = bad or not torch.isfinite(bg).all()
-        if found_inf is not None and bad:
-            found_inf[0] = 1.0
-
-    def conv_pack(self, master, out_scale, w, wd, cout, cin, taps, cin_p, cout_p, flip, bias=None, bias_out=None):
-        if bias_out is not None:
-            emul.V1(bias_out, cout).copy_(emul.V1(bias, cout) * torch.tensor(out_scale, dtype=torch.float32))
-        m = emul.V1(master, cout * cin * taps).view(cout, cin, taps) * torch.tensor(out_scale, dtype=torch.float32)
-        wp = torch.zeros(cout, taps, cin_p)
-        wp[:, :, :cin] = m.permute(0, 2, 1)
-        emul.V1(w, wp.numel()).copy_(wp.reshape(-1).to(w.dtype))
-        if wd is not None:
-            dp = torch.zeros(cin, taps, cout_p)
-            dp[:, :, :cout] = (m.flip(2) if flip else m).permute(1, 2, 0)
-            emul.V1(wd, dp.numel()).copy_(dp.reshape(-1).to(wd.dtype))
-
-
-# ---- one optimizer step of the tiny topology with trainable convolutions, against the CPU oracle ----------------------------------------
-STEP_GEOM = (1, 3, 16, 16)            # B, T, h, w
+# ---- one optimizer step of the tiny topology with trainable convolutions (selection_checks.py), against the CPU oracle -------------------
 CONV_AND_TEMPORAL = ("temporal_transformer_block", "@conv")
-_STEP_REFS = {}
-
-
-def oracle_names(orc, which):
-    """the rule of train.select_trainable, applied to the oracle (torch's own nn.Conv2d / nn.Conv3d modules)"""
-    rules = [which] if isinstance(which, str) else list(which)
-    conv = {id(p) for m in orc.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.Conv3d)) for p in m.parameters()} if "@conv" in rules else set()
-    subs = [r for r in rules if r != "@conv"]
-    return [n for n, p in orc.named_parameters() if id(p) in conv or any(r in n for r in subs)]
-
-
-def oracle_step(which, seed=3, lr=1e-4, steps=1):
-    """One torch.optim.AdamW step of the CPU oracle (fp32 autograd) with `which` trainable: loss, prediction, every gradient, the updated
-    parameters and the prediction of the updated weights.  Computed once per selection and shared."""
-    import copy
-    from oracle.step import edm_inputs, edm_loss, make_synthetic_batch
-    from oracle.unet import TINY_CONFIG, UNetSpatioTemporalConditionOracle, scaled_init_
-    key = (tuple([which] if isinstance(which, str) else which), seed, lr, steps)
-    if key in _STEP_REFS:
-        return _STEP_REFS[key]
-    cfg = TINY_CONFIG
-    B, T, h, w = STEP_GEOM
-    orc = UNetSpatioTemporalConditionOracle(**cfg)
-    scaled_init_(orc, seed)
-    names = set(oracle_names(orc, which))
-    for n, p in orc.named_parameters():
-        p.requires_grad_(n in names)
-    batch = make_synthetic_batch(B, T, h, w, seed + 1, cross_dim=cfg["cross_attention_dim"])
-    opt = torch.optim.AdamW([p for p in orc.parameters() if p.requires_grad], lr=lr, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8)
-    sd0 = copy.deepcopy(orc.state_dict())
-    unet_in, ts, ehs, ids, noisy, sig = edm_inputs(batch)
-    pred = orc(unet_in, ts, ehs, added_time_ids=ids).sample
-    loss = edm_loss(pred, noisy, batch["latents"], sig)
-    loss.backward()
-    grads = {n: p.grad.clone() for n, p in orc.named_parameters() if p.grad is not None}
-    opt.step()
-    params_after = {n: p.detach().clone() for n, p in orc.named_parameters() if p.requires_grad}
-    with torch.no_grad():
-        pred_after = orc(unet_in, ts, ehs, added_time_ids=ids).sample
-    params_after2 = None
-    if steps == 2:                                 # a second torch.optim.AdamW step on the same batch
-        opt.zero_grad()
-        edm_loss(orc(unet_in, ts, ehs, added_time_ids=ids).sample, noisy, batch["latents"], sig).backward()
-        opt.step()
-        params_after2 = {n: p.detach().clone() for n, p in orc.named_parameters() if p.requires_grad}
-    _STEP_REFS[key] = dict(params_after2=params_after2, sd0=sd0, batch=batch, inputs=(unet_in, ts, ehs, ids, noisy), loss=float(loss.detach()), pred=pred.detach(),
-                           pred_after=pred_after, lr=lr, grads=grads, params_after=params_after, names=sorted(names), traj=None)
-    return _STEP_REFS[key]
-
-
-def make_trainer(ref, which, dtype, dev, lr=None, **kw):
-    from oracle.unet import TINY_CONFIG
-    from svd_xtend_amd.train import Trainer
-    from svd_xtend_amd.unet import UNetSpatioTemporalConditionModel
-    m = UNetSpatioTemporalConditionModel(**TINY_CONFIG)
-    m.load_state_dict(ref["sd0"], strict=True)
-    m.to(dev)
-    return Trainer(m, dtype=dtype, lr=lr or ref["lr"], trainable=which, **kw)
-
-
-def step_batch(ref, dev):
-    unet_in, ts, ehs, ids, noisy = (t.to(dev) for t in ref["inputs"])
-    b = ref["batch"]
-    return dict(unet_in=unet_in, timesteps=ts, ehs=ehs, added_time_ids=ids, noisy_latents=noisy, target=b["latents"].to(dev),
-                sigmas=b["sigmas"].to(dev))
-
-
-def product_step(ref, which, dtype, dev):
-    """the same step through Trainer(trainable=which): what e2e_checks.compare / assert_parity read"""
-    tr = make_trainer(ref, which, dtype, dev)
-    m, b = tr.model, step_batch(ref, dev)
-    with torch.no_grad():
-        pred0 = m(b["unet_in"], b["timesteps"], b["ehs"], b["added_time_ids"]).sample.float().cpu()
-    tr.zero_grad()
-    tr.forward_backward(**b)
-    loss = float(tr.last_loss())
-    scale = float(tr.opt_state[1])
-    grads = {n: (p.grad.detach().float().cpu() / scale) for n, p in m.named_parameters() if p.requires_grad}
-    tr.optimizer_step()
-    params = {n: p.detach().float().cpu() for n, p in m.named_parameters() if p.requires_grad}
-    with torch.no_grad():
-        pred = m(b["unet_in"], b["timesteps"], b["ehs"], b["added_time_ids"]).sample.float().cpu()
-    return dict(loss=loss, grads=grads, params_after=params, pred=pred0, pred_after=pred, state=tr.opt_state.cpu().tolist(), trainer=tr)
 
 
 def assert_step_parity(key, ref, got, bf16=False):
@@ -392,34 +266,7 @@ def assert_step_parity(key, ref, got, bf16=False):
     assert any("temporal_res_block.conv2.weight" in n for n in conv) and "conv_in.weight" in conv and "conv_out.bias" in conv
     for n in conv:
         c = e2e_checks.cosine(got["grads"][n], ref["grads"][n])
-        assert c >= (0.995 if bf16 else 0.9995), (key, n, c)
+        assert c >= COS_BAR[bf16], (key, n, c)
     r = e2e_checks.compare(ref, got)
     e2e_checks.assert_parity(key, r, bf16=bf16)
     return r
-
-
-def run_mode(ref, which, mode: str, steps: int = 3, dtype=torch.float16, lr: float = 1e-3):
-    """`steps` optimizer steps on the device, eager (`Trainer.step`), as the captured step (train.GraphedStep: its warm-up pass is step 1)
-    or as the launch plan recorded during that capture (svdx_plan_replay): masters, moments, loss and the packed convolution weights."""
-    from svd_xtend_amd.train import GraphedStep
-    tr = make_trainer(ref, which, dtype, "cuda", lr=lr)
-    batch = step_batch(ref, "cuda")
-    if mode == "eager":
-        for _ in range(steps):
-            tr.step(batch)
-    else:
-        gs = GraphedStep(tr, batch, record_plan=mode == "plan")
-        for _ in range(steps - 1):
-            gs.replay_plan() if mode == "plan" else gs()
-    torch.cuda.synchronize()
-    packed = [op for op in tr.model._conv_ops if op.trainable]
-    return dict(p=tr.p_flat.clone(), m=tr.m_flat.clone(), v=tr.v_flat.clone(), loss=float(tr.loss_slot.cpu()), state=tr.opt_state.cpu().tolist(),
-                w=[op.w.clone() for op in packed], wd=[op.wd.clone() for op in packed if op.wd is not None])
-
-
-def assert_same_bits(a, b, what):
-    assert a["loss"] == b["loss"] and a["state"] == b["state"], (what, a["loss"], b["loss"])
-    for k in ("p", "m", "v"):
-        assert torch.equal(a[k], b[k]), (what, k, float((a[k] - b[k]).abs().max()))
-    assert len(a["w"]) == len(b["w"]) > 20 and all(torch.equal(x, y) for x, y in zip(a["w"], b["w"])), (what, "packed w")
-    assert all(torch.equal(x, y) for x, y in zip(a["wd"], b["wd"])), (what, "packed wd")

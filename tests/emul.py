@@ -4,6 +4,8 @@ TEST INFRASTRUCTURE: (1) the fp32 reference each HIP kernel is compared against 
 (2) a CPU stand-in so the host-side orchestration (explicit forward/backward schedules, packing, flat
 buffers, DP) can be checked against the oracle without a GPU.  Pointer semantics are reproduced with
 as_strided on the tensor's storage, so views with offsets behave exactly like `base + offset` pointers.
+EmuBackend emulates EVERY launching entry of kernels.HipBackend (tests/test_emul_complete.py holds the two to the same signatures);
+`record` logs the calls a backend instance receives, with the depth that tells a launch from a call inside an emulation.
 """
 import math
 
@@ -12,6 +14,37 @@ import torch
 from svd_xtend_amd import kernels as K
 
 GN_REPLICAS = K.GN_REPLICAS
+
+
+class Log(list):
+    """What `record` fills: ("svdx_<entry>", depth) in call order.  `on = False` pauses the recording, `clear()` starts a new phase."""
+    on = True
+
+    def names(self, depth=None):
+        return [n for n, d in self if depth is None or d == depth]
+
+
+def record(be) -> Log:
+    """Wrap every public callable of the backend INSTANCE `be` (instance attributes, so that the calls an emulation makes on `self` are
+    seen too) and return the log.  Depth 0 is a call the host issued -- a launch; depth >= 1 is a call an emulation made internally (the
+    singles under a `*_batch` entry, svdx_gemm_tn under svdx_gemm_tn_gather), which the device never sees.  A HipBackend or a SimBackend
+    only ever shows depth 0."""
+    log, depth = Log(), [0]
+
+    def wrap(name, f):
+        def call(*a, **kw):
+            if log.on:
+                log.append(("svdx_" + name, depth[0]))
+            depth[0] += 1
+            try:
+                return f(*a, **kw)
+            finally:
+                depth[0] -= 1
+        return call
+    for name in dir(be):
+        if not name.startswith("_") and callable(getattr(be, name)):
+            setattr(be, name, wrap(name, getattr(be, name)))
+    return log
 
 
 def V(t, rows, cols, ld):
@@ -110,6 +143,48 @@ def gn_encode_add(stats, n_s, G, cnt, mode, s0, s1):
     v[0, ..., 1] += torch.round(s1.double() * 2.0 ** k1).to(torch.int64)
 
 
+def latent_statements(mean, std, first, eps, noise, cond_mean, cond_std, sigma, den, keep, scaling):
+    """DEFINES the result of svdx_latent_batch (every comparison with it is torch.equal): the statements TrainLoop._compute, edm_prepare
+    and conditioning_dropout execute, over a cache: every operator one rounded fp32 operation.  mean / std [F, c, h, w]; first int64 [B], clamped into [0, F - T] as the kernel does; -> unet_in, noisy, target."""
+    B, T = noise.shape[:2]
+    F = mean.shape[0]
+    rows = first.clamp(0, F - T)[:, None] + torch.arange(T, device=first.device)[None]
+    lat = (mean[rows] + std[rows] * eps[:, :T]) * scaling
+    cond = keep.view(B, 1, 1, 1) * (((cond_mean + cond_std * eps[:, T]) * scaling) / scaling)
+    noisy = lat + noise * sigma.view(B, 1, 1, 1, 1)
+    inp = noisy / den.view(B, 1, 1, 1, 1)
+    return torch.cat([inp, cond.unsqueeze(1).repeat(1, T, 1, 1, 1)], dim=2), noisy, lat
+
+
+def rb16_f64(x: float) -> float:
+    """x >= 0 correctly rounded to bf16 from float64 (ties to even), as the kernel's rb16_f64."""
+    if not math.isfinite(x) or x == 0.0:
+        return x
+    e = max(math.frexp(x)[1] - 1, -126)
+    q = 2.0 ** (e - 7)
+    return torch.tensor(round(x / q) * q, dtype=torch.float64).float().item()
+
+
+def rb16(x: float) -> float:
+    return torch.tensor(x, dtype=torch.float32).to(torch.bfloat16).float().item()
+
+
+def f32(x: float) -> float:
+    return torch.tensor(x, dtype=torch.float64).float().item()
+
+
+def coef_from_sums(tensor_sums, max_norm, unscale, ref):
+    """(total_norm, coef) from per-tensor float64 sums of squares, the arithmetic svdx_grad_clip_coef documents."""
+    if ref:
+        tot = sum(rb16_f64(math.sqrt(s) * unscale) ** 2 for s in tensor_sums)
+        norm = rb16_f64(math.sqrt(tot))
+        coef = rb16(rb16(f32(1.0 / rb16(f32(norm + rb16_f64(1e-6))))) * f32(max_norm))
+    else:
+        norm = f32(math.sqrt(sum(tensor_sums)) * unscale)
+        coef = f32(max_norm / (norm + 1e-6))
+    return norm, (1.0 if coef > 1.0 else coef)
+
+
 class EmuBackend:
     # ---- GEMM family ----
     def gemm(self, A, B, C, M, N, Kd, lda, ldb, ldc, bias=None, rowvec=None, rv_ld=0, rv_rpg=0, rv_mod=0,
@@ -202,6 +277,44 @@ class EmuBackend:
             c += v
         if found_inf is not None and not torch.isfinite(c).all():
             found_inf[0] = 1.0
+
+    def gemm_tn_gather(self, A, X, C, R, N, lda, ldc, gather, out_mode=K.OUT_F32_SLAB, split_k=1, a_colsum=None, stages=0, found_inf=None):
+        Kd = (3 if gather.mode == K.GATHER_TEMPORAL3 else 9) * gather.cin
+        assert gather.mode in (K.GATHER_CONV3X3, K.GATHER_TEMPORAL3) and gather.cin % 8 == 0
+        aeff = gather_rows(X, gather, R).to(A.dtype).contiguous()
+        self.gemm_tn(A, aeff, C, R, N, Kd, lda, Kd, ldc, out_mode=out_mode, split_k=split_k, a_colsum=a_colsum, stages=stages, found_inf=found_inf)
+
+    def conv_wgrad_finalize(self, acc, nsplit, slab_stride, ld_acc, w_grad, cout, cin, cin_p, taps, alpha=1.0, store=True, colsum_slabs=None,
+                            colsum_ld=0, b_grad=None, found_inf=None):
+        v = torch.zeros(cout, taps, cin, device=acc.device)
+        for z in range(nsplit):
+            sl = torch.as_strided(acc, (cout, ld_acc), (ld_acc, 1), acc.storage_offset() + z * slab_stride)
+            v = v + sl[:, :taps * cin_p].reshape(cout, taps, cin_p)[:, :, :cin]
+        v = (v * alpha).permute(0, 2, 1).reshape(-1)
+        wg = V1(w_grad, cout * cin * taps)
+        wg.copy_(v) if store else wg.add_(v)
+        bad = not torch.isfinite(wg).all()
+        if b_grad is not None:
+            s = torch.zeros(cout, device=acc.device)
+            for z in range(nsplit):
+                s = s + V1(colsum_slabs, nsplit * colsum_ld)[z * colsum_ld:z * colsum_ld + cout]
+            bg = V1(b_grad, cout)
+            bg.copy_(s * alpha) if store else bg.add_(s * alpha)
+            bad = bad or not torch.isfinite(bg).all()
+        if found_inf is not None and bad:
+            found_inf[0] = 1.0
+
+    def conv_pack(self, master, out_scale, w, wd, cout, cin, taps, cin_p, cout_p, flip, bias=None, bias_out=None):
+        if bias_out is not None:
+            V1(bias_out, cout).copy_(V1(bias, cout) * torch.tensor(out_scale, dtype=torch.float32))
+        m = V1(master, cout * cin * taps).view(cout, cin, taps) * torch.tensor(out_scale, dtype=torch.float32)
+        wp = torch.zeros(cout, taps, cin_p)
+        wp[:, :, :cin] = m.permute(0, 2, 1)
+        V1(w, wp.numel()).copy_(wp.reshape(-1).to(w.dtype))
+        if wd is not None:
+            dp = torch.zeros(cin, taps, cout_p)
+            dp[:, :, :cout] = (m.flip(2) if flip else m).permute(1, 2, 0)
+            V1(wd, dp.numel()).copy_(dp.reshape(-1).to(wd.dtype))
 
     def gemm_finalize(self, acc, nsplit, slab_stride, C, M, N, ldc, bias=None, rowvec=None, rv_ld=0, rv_rpg=0, rv_mod=0,
                       res=None, ldres=0, accumulate_f32=False, dtype=None, colsum_slabs=None, colsum_out=None, gn=None):
@@ -335,6 +448,25 @@ class EmuBackend:
         if add is not None:
             d = d + V(add, n_s * rows, C, C).float()
         V(dx, n_s * rows, C, C).copy_(d.to(dx.dtype))
+
+    def gn_bwd_stats_affine(self, dy, x, stats, gamma, beta, bstats, dgamma, dbeta, partial, n_s, rows, C, G, eps, silu_, prezeroed=0,
+                            defer_reduce=False):
+        xf, mean, rstd, _ = self._gn_parts(x, stats, n_s, rows, C, G, eps)
+        xhat = ((xf - mean) * rstd).reshape(n_s, rows, C)
+        dz = V(dy, n_s * rows, C, C).float().view(n_s, rows, C)
+        if silu_:
+            dz = dz * silu_grad(xhat * V1(gamma, C) + V1(beta, C))
+        dzg = (dz * V1(gamma, C)).view(n_s, rows, G, C // G)
+        if not prezeroed:
+            gn_view(bstats, n_s, G).zero_()
+        gn_encode_add(bstats, n_s, G, rows * (C // G), 1, dzg.sum((1, 3)), (dzg * xhat.view(n_s, rows, G, C // G)).sum((1, 3)))
+        nblk = K.gn_bwd_blocks(n_s, rows, C, G)
+        pt = V(partial, nblk, 2 * C, 2 * C)          # the totals in row 0, zeros below (as the emulation of svdx_ln_bwd leaves them)
+        pt.zero_()
+        pt[0, :C] = (dz * xhat).sum((0, 1))
+        pt[0, C:] = dz.sum((0, 1))
+        if not defer_reduce:
+            self.ln_param_reduce_batch([(partial, dgamma, dbeta, nblk, C)])
 
     # ---- LayerNorm ----
     def ln_fwd(self, x, gamma, beta, y, stats, rows, C, eps):
@@ -719,3 +851,25 @@ class EmuBackend:
         self._adamw_update(P, G, Mm, Vv, float(st[4]) * grad_mul, lr, beta1, beta2, eps, wd, lr / float(st[5]), math.sqrt(float(st[6])), param_mode)
         if p_act is not None:
             V1(p_act, n).copy_(P.to(p_act.dtype))
+
+    # ---- latent cache ----
+    def latent_batch(self, mean, std, first, eps, noise, cond_mean, cond_std, sigma, den, keep, scaling, unet_in, noisy, target):
+        u, n, t = latent_statements(mean, std, first, eps, noise, cond_mean, cond_std, sigma, den, keep, scaling)
+        unet_in.copy_(u)
+        noisy.copy_(n)
+        target.copy_(t)
+
+    # ---- gradient-norm clipping (float64 on the host, the kernels' arithmetic) ----
+    def grad_sumsq_spans(self, g, spans, n_spans, partial):
+        flat = g.reshape(-1)
+        for s, (off, cnt, _) in enumerate(spans[:n_spans].view(-1, 3).tolist()):
+            partial[s] = flat[off:off + cnt].double().pow(2).sum()
+
+    def grad_clip_coef(self, partial, spans, n_spans, n_tensors, max_norm, grad_mul, opt_state, out, param_mode=K.PARAMS_F32):
+        sums = [0.0] * n_tensors
+        for s, (_, _, t) in enumerate(spans[:n_spans].view(-1, 3).tolist()):
+            sums[t] += float(partial[s])
+        norm, coef = coef_from_sums(sums, max_norm, float(opt_state[4]) * grad_mul, param_mode == K.PARAMS_BF16_REFERENCE)
+        out[0], out[1] = norm, coef
+        if not float(opt_state[7]) > 0:
+            opt_state[4] = opt_state[4] * torch.tensor(coef, dtype=torch.float32)

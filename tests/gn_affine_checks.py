@@ -1,22 +1,21 @@
 """Shared checks of the GroupNorm affine gradients (svdx_gn_bwd_stats_affine, svdx_gn_bwd_blocks): the kernel cases, their float64
-reference (autograd through F.group_norm (+ F.silu)), the per-channel error bound, the emulation backend, and the runners the simulator
-(tests/test_gn_affine.py) and the device (tests/test_gn_affine_gpu.py) both use.  TEST INFRASTRUCTURE."""
+reference (autograd through F.group_norm (+ F.silu)), the per-channel error bound, and the runners the simulator
+(tests/test_gn_affine.py) and the device (tests/test_gn_affine_gpu.py) both use.  The emulation of the entry is emul.EmuBackend's; the
+step against the oracle is selection_checks.py's.  TEST INFRASTRUCTURE."""
 from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
 
 import census
-import conv_wgrad_checks as cw
-import emul
 import ref64
 from census import _ratio, ulp_of
+from conv_wgrad_checks import DT, banded, bands_intact
 from kernel_checks import tol_for
+from selection_checks import COS_BAR, gn_names
 from svd_xtend_amd import kernels as K
 
 G = 32
-DT = cw.DT
-banded, bands_intact = cw.banded, cw.bands_intact
 
 
 class Case(NamedTuple):
@@ -196,89 +195,17 @@ def sweep_case(be, dev, c: Case, dt: torch.dtype, verbose: bool = False):
     return [run_case(be, dev, c, dt, silu, eps, verbose=verbose) for silu, eps in VARIANTS]
 
 
-# ---- the emulation of the new entries -------------------------------------------------------------------------------------------------
-class GnAffineEmuBackend(cw.ConvWgradEmuBackend):
-    """emul.EmuBackend (+ the convolution entries) + svdx_gn_bwd_stats_affine; `log` receives the entry name of every call."""
-
-    def __init__(self):
-        self.log = None
-
-    def __getattribute__(self, name):
-        v = object.__getattribute__(self, name)
-        if name.startswith("_") or name == "log" or not callable(v):
-            return v
-        log = object.__getattribute__(self, "log")
-        if log is None:
-            return v
-
-        def call(*a, **kw):
-            log.append("svdx_" + name)
-            return v(*a, **kw)
-        return call
-
-    def gn_bwd_stats_affine(self, dy, x, stats, gamma, beta, bstats, dgamma, dbeta, partial, n_s, rows, C, G, eps, silu_, prezeroed=0,
-                            defer_reduce=False):
-        xf, mean, rstd, _ = self._gn_parts(x, stats, n_s, rows, C, G, eps)
-        xhat = ((xf - mean) * rstd).reshape(n_s, rows, C)
-        dz = emul.V(dy, n_s * rows, C, C).float().view(n_s, rows, C)
-        if silu_:
-            dz = dz * emul.silu_grad(xhat * emul.V1(gamma, C) + emul.V1(beta, C))
-        dzg = (dz * emul.V1(gamma, C)).view(n_s, rows, G, C // G)
-        if not prezeroed:
-            emul.gn_view(bstats, n_s, G).zero_()
-        emul.gn_encode_add(bstats, n_s, G, rows * (C // G), 1, dzg.sum((1, 3)), (dzg * xhat.view(n_s, rows, G, C // G)).sum((1, 3)))
-        nblk = K.gn_bwd_blocks(n_s, rows, C, G)
-        pt = emul.V(partial, nblk, 2 * C, 2 * C)          # the totals in row 0, zeros below (as the emulation of svdx_ln_bwd leaves them)
-        pt.zero_()
-        pt[0, :C] = (dz * xhat).sum((0, 1))
-        pt[0, C:] = dz.sum((0, 1))
-        if not defer_reduce:
-            object.__getattribute__(self, "ln_param_reduce_batch")([(partial, dgamma, dbeta, nblk, C)])
-
-
-# ---- one optimizer step of the tiny topology with trainable GroupNorm affines, against the CPU oracle ---------------------------------
-STEP_GEOM = cw.STEP_GEOM
+# ---- one optimizer step of the tiny topology with trainable GroupNorm affines (selection_checks.py), against the CPU oracle -------------
 TEMPORAL_NORM = ("temporal_transformer_block", "@norm")
 ALL_THREE = ("temporal_transformer_block", "@conv", "@norm")
 SELECTIONS = [TEMPORAL_NORM, "@norm", ALL_THREE, "conv_norm_out"]
-_STEP_REFS = {}
 
-
-def oracle_names(orc, which):
-    """the rule of train.select_trainable, applied to the oracle (torch's own nn.Conv2d / nn.Conv3d / nn.GroupNorm modules)"""
-    rules = [which] if isinstance(which, str) else list(which)
-    pick = set()
-    if "@conv" in rules:
-        pick |= {id(p) for m in orc.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.Conv3d)) for p in m.parameters()}
-    if "@norm" in rules:
-        pick |= {id(p) for m in orc.modules() if isinstance(m, torch.nn.GroupNorm) for p in m.parameters()}
-    subs = [r for r in rules if r not in ("@conv", "@norm")]
-    return [n for n, p in orc.named_parameters() if id(p) in pick or any(r in n for r in subs)]
-
-
-def oracle_step(which, seed=3, lr=1e-4):
-    """conv_wgrad_checks.oracle_step with this module's selection rule ("@norm"); computed once per selection and shared"""
-    key = (tuple([which] if isinstance(which, str) else which), seed, lr)
-    if key not in _STEP_REFS:
-        prev = cw.oracle_names
-        cw.oracle_names = oracle_names
-        try:
-            _STEP_REFS[key] = cw.oracle_step(which, seed=seed, lr=lr)
-        finally:
-            cw.oracle_names = prev
-    return _STEP_REFS[key]
-
-
-def gn_names(orc_or_model):
-    return sorted(f"{mn}.{pn}" for mn, m in orc_or_model.named_modules() if isinstance(m, torch.nn.GroupNorm) for pn, _ in m.named_parameters())
-
-
-# (launches, sha256 of the newline-joined entry names) of one Trainer.step of the tiny topology with the DEFAULT trainable set, recorded
-# on the commit before the GroupNorm affines became trainable, through GnAffineEmuBackend.log: the default set must keep issuing exactly these
+# (calls, sha256 of the newline-joined entry names) of one Trainer.step of the tiny topology with the DEFAULT trainable set, recorded on
+# the commit before the GroupNorm affines became trainable: the calls the emulation receives at ALL depths of emul.record, the 154 an
+# emulation makes on itself included (80 svdx_small_linear and 64 svdx_outer_acc under their *_batch entries, 10 svdx_tattn_fwd under
+# svdx_tsa_fwd).  The default set must keep issuing exactly these; the launches among them -- depth 0 -- are DEFAULT_LAUNCHES
 PARENT_DEFAULT_LAUNCHES = (1595, "9de55de4aa1df7844284555f4b3413ee0e090e5288f95d01566524ecb678950e")
-
-# the project's bars on the cosine of a gradient tensor against the oracle (e2e_checks.assert_parity)
-COS_BAR = {False: 0.9995, True: 0.995}
+DEFAULT_LAUNCHES = 1441
 
 
 def assert_step_parity(key, ref, got, bf16=False, emu=None):
@@ -302,16 +229,3 @@ def assert_step_parity(key, ref, got, bf16=False, emu=None):
     r = e2e_checks.compare(ref, got)
     e2e_checks.assert_parity(key, r, bf16=bf16)
     return r
-
-
-def run_mode(ref, which, mode: str, steps: int = 3, dtype=torch.float16, lr: float = 1e-3):
-    """conv_wgrad_checks.run_mode (eager / captured step / launch-plan replay) for a selection with "@norm" """
-    return cw.run_mode(ref, which, mode, steps=steps, dtype=dtype, lr=lr)
-
-
-def assert_same_bits(a, b, what):
-    assert a["loss"] == b["loss"] and a["state"] == b["state"], (what, a["loss"], b["loss"])
-    for k in ("p", "m", "v"):
-        assert torch.equal(a[k], b[k]), (what, k, float((a[k] - b[k]).abs().max()))
-    assert len(a["w"]) == len(b["w"]) and all(torch.equal(x, y) for x, y in zip(a["w"], b["w"])), (what, "packed w")
-    assert all(torch.equal(x, y) for x, y in zip(a["wd"], b["wd"])), (what, "packed wd")

@@ -1,38 +1,15 @@
 """Shared checks of the latent cache (svd_xtend_amd/latent_cache.py, svdx_latent_batch): the torch statement block that DEFINES the
-kernel's result, the emulation backend built on it, and the kernel cases the simulator (tests/test_latent_cache.py) and the device
-(tests/test_latent_cache_gpu.py) both run.  TEST INFRASTRUCTURE."""
+kernel's result (`statements`: it lives in tests/emul.py, whose EmuBackend.latent_batch is built on it) and the kernel cases the
+simulator (tests/test_latent_cache.py) and the device (tests/test_latent_cache_gpu.py) both run.  TEST INFRASTRUCTURE."""
 import itertools
 
 import torch
 
-import emul
+from emul import latent_statements as statements
 
 SENTINEL = 12345.678
 GUARD = 64                       # floats of sentinel on either side of every buffer (256 bytes: keeps the payload 16-byte aligned)
 SIGMAS = (1.3e-2, 1.0, 3e2)      # the +-5 sigma range of the loop's draw exp(N(0.7, 1.6))
-
-
-def statements(mean, std, first, eps, noise, cond_mean, cond_std, sigma, den, keep, scaling):
-    """The statements TrainLoop._compute, edm_prepare and conditioning_dropout execute, over a cache: every operator one rounded fp32
-    operation.  mean / std [F, c, h, w]; first int64 [B], clamped into [0, F - T] as the kernel does; -> unet_in, noisy, target."""
-    B, T = noise.shape[:2]
-    F = mean.shape[0]
-    rows = first.clamp(0, F - T)[:, None] + torch.arange(T, device=first.device)[None]
-    lat = (mean[rows] + std[rows] * eps[:, :T]) * scaling
-    cond = keep.view(B, 1, 1, 1) * (((cond_mean + cond_std * eps[:, T]) * scaling) / scaling)
-    noisy = lat + noise * sigma.view(B, 1, 1, 1, 1)
-    inp = noisy / den.view(B, 1, 1, 1, 1)
-    return torch.cat([inp, cond.unsqueeze(1).repeat(1, T, 1, 1, 1)], dim=2), noisy, lat
-
-
-class LatentEmuBackend(emul.EmuBackend):
-    """emul.EmuBackend + the one entry the latent cache adds."""
-
-    def latent_batch(self, mean, std, first, eps, noise, cond_mean, cond_std, sigma, den, keep, scaling, unet_in, noisy, target):
-        u, n, t = statements(mean, std, first, eps, noise, cond_mean, cond_std, sigma, den, keep, scaling)
-        unet_in.copy_(u)
-        noisy.copy_(n)
-        target.copy_(t)
 
 
 # ---- kernel cases ---------------------------------------------------------------------------------------------------------------

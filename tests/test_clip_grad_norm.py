@@ -24,6 +24,7 @@ for _p in (ROOT, HERE, os.path.join(HERE, "sim")):
         sys.path.insert(0, _p)
 
 import clip_checks as cc  # noqa: E402
+import emul  # noqa: E402
 from svd_xtend_amd import kernels as K  # noqa: E402
 
 SUM_REL = 1e-11
@@ -180,15 +181,6 @@ def _batch(seed, T=3):
     return dict(unet_in=unet_in, timesteps=ts, ehs=ehs, added_time_ids=ids, noisy_latents=noisy, target=b["latents"], sigmas=b["sigmas"])
 
 
-@pytest.fixture
-def clip_emu():
-    prev = K._backend
-    be = cc.ClipEmuBackend()
-    K._set_backend_for_tests(be)
-    yield be
-    K._set_backend_for_tests(prev)
-
-
 def _one_step(max_grad_norm, batch, dtype=torch.float16):
     from svd_xtend_amd.train import Trainer
     tr = Trainer(_model(0), dtype=dtype, lr=1e-3, max_grad_norm=max_grad_norm)
@@ -199,12 +191,14 @@ def _one_step(max_grad_norm, batch, dtype=torch.float16):
                     w16=tr.rt.w16_flat.clone(), wt16=tr.rt.wt16_flat[:tr.rt.wt_pos].clone() if tr.rt.wt16_flat is not None else None)   # (the arena beyond wt_pos is unused)
 
 
-def test_trainer_clipping_is_opt_in_and_scales_the_update(clip_emu):
+def test_trainer_clipping_is_opt_in_and_scales_the_update(emu_backend):
+    rec = emul.record(K._backend)
+    clip_calls = lambda: [e for e in rec.names(depth=0) if e in ("svdx_grad_sumsq_spans", "svdx_grad_clip_coef")]   # noqa: E731
     b = _batch(7)
     tr0, none = _one_step(None, b)
-    assert clip_emu.clip_calls == [] and tr0.grad_norm is None and tr0.clip_coef is None
+    assert clip_calls() == [] and tr0.grad_norm is None and tr0.clip_coef is None
     tr1, huge = _one_step(1e30, b)
-    assert clip_emu.clip_calls == ["svdx_grad_sumsq_spans", "svdx_grad_clip_coef"]
+    assert clip_calls() == ["svdx_grad_sumsq_spans", "svdx_grad_clip_coef"]
     assert float(tr1.clip_coef) == 1.0 and tr1.grad_norm.dim() == 0
     for k in none:
         assert (none[k] is None and huge[k] is None) or torch.equal(none[k], huge[k]), k
@@ -229,9 +223,9 @@ def _rank_worker(rank, world, port, out, max_grad_norm):
     for p in (ROOT, HERE):
         if p not in sys.path:
             sys.path.insert(0, p)
-    import clip_checks
+    import emul
     from svd_xtend_amd import kernels
-    kernels._set_backend_for_tests(clip_checks.ClipEmuBackend())
+    kernels._set_backend_for_tests(emul.EmuBackend())
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from svd_xtend_amd.train import Trainer
     tr = Trainer(_model(0), dtype=torch.float32, lr=1e-3, max_grad_norm=max_grad_norm)

@@ -1,5 +1,5 @@
 """CPU (`-m "not gpu"`): the convolution weight gradient -- svdx_gemm_tn_gather + svdx_conv_wgrad_finalize and svdx_conv_pack -- with the
-kernel sources executed by the simulator of tests/sim/ and with the emulation of tests/conv_wgrad_checks.py, against the float64
+kernel sources executed by the simulator of tests/sim/ and with the emulation of tests/emul.py, against the float64
 reference (autograd through the float64 convolutions of tests/ref64.py) under the census' svdx_gemm_tn bound."""
 import os
 import sys
@@ -11,6 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "sim"))
 
 import conv_wgrad_checks as cw  # noqa: E402
+import emul  # noqa: E402
+import selection_checks as sc  # noqa: E402
 from svd_xtend_amd import kernels as K  # noqa: E402
 
 
@@ -25,15 +27,6 @@ def sim_installed(sim):
     prev = K._backend
     K._set_backend_for_tests(sim)
     yield sim
-    K._set_backend_for_tests(prev)
-
-
-@pytest.fixture
-def emu_installed():
-    prev = K._backend
-    be = cw.ConvWgradEmuBackend()
-    K._set_backend_for_tests(be)
-    yield be
     K._set_backend_for_tests(prev)
 
 
@@ -57,7 +50,7 @@ def test_kernel_case_on_simulator(sim, name, dt):
 def test_emulation_meets_the_same_reference(name):
     """SELF-CHECK of the test double, not of the feature (it passes without the library's new entries): the emulation subclass the step
     tests run on meets the float64 reference under the same bound, so a step that passes on it says something about the host code."""
-    cw.sweep_case(cw.ConvWgradEmuBackend(), "cpu", cw.BY_NAME[name], torch.float16)
+    cw.sweep_case(emul.EmuBackend(), "cpu", cw.BY_NAME[name], torch.float16)
 
 
 def test_a_dropped_tap_or_a_zero_result_cannot_pass():
@@ -121,7 +114,7 @@ def _trainable_op(c, dev, seed=0):
 
 
 @pytest.mark.parametrize("name", ["3x3_s2_8x8", "3x3_ups_4x4", "3x3_conv_out_cout4", "3x3_conv_in_cin8", "t3_T3_c64", "3x3_s1_16x16_split8"])
-def test_convop_bwd_dw_on_emulation(emu_installed, name):
+def test_convop_bwd_dw_on_emulation(emu_backend, name):
     """ConvOp.bwd_dw (store on the first micro-batch, += on the second) against the float64 reference, the alpha of the case folded in as
     the packed out_scale; conv_out runs at N = cout_p and keeps its 4 rows"""
     from svd_xtend_amd import ops
@@ -151,7 +144,7 @@ def test_convop_bwd_dw_on_emulation(emu_installed, name):
     assert float(rt.found_inf) == 1.0
 
 
-def test_convop_refresh_follows_the_master(emu_installed):
+def test_convop_refresh_follows_the_master(emu_backend):
     """after the master moved, refresh leaves exactly what a fresh pack of the new master gives"""
     from svd_xtend_amd import ops
     c = cw.BY_NAME["t3_T3_c64"]
@@ -170,9 +163,9 @@ def test_convop_refresh_follows_the_master(emu_installed):
 
 
 # ---- the step: Trainer(trainable=...) on the emulation against the CPU oracle --------------------------------------------------------------
-def test_step_with_convolutions_and_temporal_blocks_matches_oracle(emu_installed):
-    ref = cw.oracle_step(cw.CONV_AND_TEMPORAL)
-    got = cw.product_step(ref, cw.CONV_AND_TEMPORAL, torch.float16, torch.device("cpu"))
+def test_step_with_convolutions_and_temporal_blocks_matches_oracle(emu_backend):
+    ref = sc.oracle_step(cw.CONV_AND_TEMPORAL)
+    got = sc.product_step(ref, cw.CONV_AND_TEMPORAL, torch.float16, torch.device("cpu"))
     r = cw.assert_step_parity("emulation conv+temporal float16", ref, got)
     print(r)
     tr = got["trainer"]
@@ -187,13 +180,13 @@ def test_step_with_convolutions_and_temporal_blocks_matches_oracle(emu_installed
             assert not any(lo < off + p.numel() and off < hi for lo, hi in tr._buckets.values()), conv[id(p)]
 
 
-def test_a_second_sweep_after_zero_grad_gives_the_same_gradients(emu_installed):
+def test_a_second_sweep_after_zero_grad_gives_the_same_gradients(emu_backend):
     """zero_grad(); forward_backward(batch) twice on one batch, no optimizer step between: every gradient comes out bit-equal.  A slot
     that is neither stored by its producer nor zeroed would double -- the 1x1 shortcuts' bias gradients did (their column sums go through
     gemm_tn_acc, which accumulates), so their biases must stay out of Runtime.write_once while the 3x3 / temporal ones are in it."""
-    ref = cw.oracle_step(cw.CONV_AND_TEMPORAL)
-    tr = cw.make_trainer(ref, cw.CONV_AND_TEMPORAL, torch.float16, torch.device("cpu"))
-    batch = cw.step_batch(ref, "cpu")
+    ref = sc.oracle_step(cw.CONV_AND_TEMPORAL)
+    tr = sc.make_trainer(ref, cw.CONV_AND_TEMPORAL, torch.float16, torch.device("cpu"))
+    batch = sc.step_batch(ref, "cpu")
     sweeps = []
     for _ in range(2):
         tr.zero_grad()
@@ -208,12 +201,12 @@ def test_a_second_sweep_after_zero_grad_gives_the_same_gradients(emu_installed):
     assert any(op.kind == "1x1" for op in ops_) and all(id(op.weight) in tr.rt.write_once for op in ops_ if op.trainable)
 
 
-def test_two_optimizer_steps_match_the_oracle(emu_installed):
+def test_two_optimizer_steps_match_the_oracle(emu_backend):
     """the second step starts from gradients the first one left behind: after two steps on one batch every trainable tensor has moved as
     the oracle's (torch.optim.AdamW), the shortcut biases included"""
-    ref = cw.oracle_step(cw.CONV_AND_TEMPORAL, steps=2)
-    tr = cw.make_trainer(ref, cw.CONV_AND_TEMPORAL, torch.float32, torch.device("cpu"))
-    batch = cw.step_batch(ref, "cpu")
+    ref = sc.oracle_step(cw.CONV_AND_TEMPORAL, steps=2)
+    tr = sc.make_trainer(ref, cw.CONV_AND_TEMPORAL, torch.float32, torch.device("cpu"))
+    batch = sc.step_batch(ref, "cpu")
     for _ in range(2):
         tr.step(batch)
     lr = ref["lr"]
@@ -221,16 +214,16 @@ def test_two_optimizer_steps_match_the_oracle(emu_installed):
         if p.requires_grad:
             d = (p.detach() - ref["params_after2"][n]).abs()
             assert float(d.max()) <= 2.5 * lr and float(d.mean()) <= 0.05 * lr, (n, float(d.max()), float(d.mean()))
-    sc = [n for n in ref["names"] if "conv_shortcut.bias" in n]
-    moved = [float((ref["params_after2"][n] - ref["sd0"][n]).abs().mean()) for n in sc]
-    assert sc and min(moved) > 0.5 * lr                      # (they do move: a doubled gradient would show in the update's direction only)
+    short = [n for n in ref["names"] if "conv_shortcut.bias" in n]
+    moved = [float((ref["params_after2"][n] - ref["sd0"][n]).abs().mean()) for n in short]
+    assert short and min(moved) > 0.5 * lr                   # (they do move: a doubled gradient would show in the update's direction only)
 
 
-def test_step_with_convolutions_alone(emu_installed):
+def test_step_with_convolutions_alone(emu_backend):
     """trainable="@conv": no attention block trains, every module behind conv_in still needs its input gradient, the skips carry
     gradients, and the gradients match the oracle"""
-    ref = cw.oracle_step("@conv")
-    got = cw.product_step(ref, "@conv", torch.float16, torch.device("cpu"))
+    ref = sc.oracle_step("@conv")
+    got = sc.product_step(ref, "@conv", torch.float16, torch.device("cpu"))
     cw.assert_step_parity("emulation conv float16", ref, got)
     m = got["trainer"].model
     assert not any(mod.has_trainable() for kind, mod in m.steps if kind == "attn")
@@ -238,13 +231,13 @@ def test_step_with_convolutions_alone(emu_installed):
     assert all(m._skip_needs_grad) and m._any_trainable
 
 
-def test_trainable_tail_only_skips_the_data_gradients_it_does_not_need(emu_installed):
+def test_trainable_tail_only_skips_the_data_gradients_it_does_not_need(emu_backend):
     """only the LAST resnet's convolutions train: nothing upstream needs a gradient, so that block runs its weight gradients with
     need_dx == False and the sweep stops there"""
     which = "up_blocks.3.resnets.2.spatial_res_block.conv"
-    ref = cw.oracle_step(which)
+    ref = sc.oracle_step(which)
     assert len(ref["names"]) == 6                                    # conv1, conv2, conv_shortcut: weight and bias
-    got = cw.product_step(ref, which, torch.float16, torch.device("cpu"))
+    got = sc.product_step(ref, which, torch.float16, torch.device("cpu"))
     import e2e_checks
     for n in ref["names"]:
         assert e2e_checks.cosine(got["grads"][n], ref["grads"][n]) >= 0.9995, n
@@ -255,18 +248,18 @@ def test_trainable_tail_only_skips_the_data_gradients_it_does_not_need(emu_insta
     assert blk.has_trainable() and not any(mod.need_dx for mod in upto) and not any(m._skip_needs_grad)
 
 
-def test_conv_out_alone_computes_no_data_gradient(emu_installed, monkeypatch):
+def test_conv_out_alone_computes_no_data_gradient(emu_backend, monkeypatch):
     """only conv_out trains: its weight gradient matches the oracle and the sweep stops there (no data-gradient GEMM, no norm backward)"""
     import e2e_checks
     from svd_xtend_amd import ops
-    ref = cw.oracle_step("conv_out")
+    ref = sc.oracle_step("conv_out")
     assert ref["names"] == ["conv_out.bias", "conv_out.weight"]
 
     def never(*a, **k):
         raise AssertionError("a data gradient nobody needs was computed")
     monkeypatch.setattr(ops.ConvOp, "bwd_dx", never)
     monkeypatch.setattr(ops.GroupNormOp, "bwd", never)
-    got = cw.product_step(ref, "conv_out", torch.float16, torch.device("cpu"))
+    got = sc.product_step(ref, "conv_out", torch.float16, torch.device("cpu"))
     for n in ref["names"]:
         assert e2e_checks.cosine(got["grads"][n], ref["grads"][n]) >= 0.9995, n
     m = got["trainer"].model
@@ -274,12 +267,12 @@ def test_conv_out_alone_computes_no_data_gradient(emu_installed, monkeypatch):
     assert all(mod.sv is None for kind, blk in m.steps if kind == "res" for mod in (blk.spatial_res_block, blk.temporal_res_block))
 
 
-def test_planted_nonfinite_conv_gradient_skips_the_step(emu_installed, monkeypatch):
+def test_planted_nonfinite_conv_gradient_skips_the_step(emu_backend, monkeypatch):
     """one inf in the gradient that reaches a convolution's weight-gradient launch: the step is skipped -- masters, moments and the packed
     16-bit weights keep every bit (the re-pack of an unchanged master gives the same bits)"""
     from svd_xtend_amd import ops
-    ref = cw.oracle_step(cw.CONV_AND_TEMPORAL)
-    tr = cw.make_trainer(ref, cw.CONV_AND_TEMPORAL, torch.float16, torch.device("cpu"))
+    ref = sc.oracle_step(cw.CONV_AND_TEMPORAL)
+    tr = sc.make_trainer(ref, cw.CONV_AND_TEMPORAL, torch.float16, torch.device("cpu"))
     target = tr.model.mid_block.resnets[0].temporal_res_block.c2
     packed = [op for op in tr.model._conv_ops if op.trainable]
     before = dict(p=tr.p_flat.clone(), m=tr.m_flat.clone(), v=tr.v_flat.clone(), w=[op.w.clone() for op in packed], wd=[op.wd.clone() for op in packed if op.wd is not None])
@@ -292,22 +285,22 @@ def test_planted_nonfinite_conv_gradient_skips_the_step(emu_installed, monkeypat
             hit.append(1)
         return bwd_dw(self, rt, dy, x, *a, **k)
     monkeypatch.setattr(ops.ConvOp, "bwd_dw", planted)
-    tr.step(cw.step_batch(ref, "cpu"))
+    tr.step(sc.step_batch(ref, "cpu"))
     assert hit and float(tr.opt_state[7]) == 1.0 and float(tr.opt_state[0]) == 0.0
     assert torch.equal(tr.p_flat, before["p"]) and torch.equal(tr.m_flat, before["m"]) and torch.equal(tr.v_flat, before["v"])
     assert all(torch.equal(op.w, w) for op, w in zip(packed, before["w"]))
     assert all(torch.equal(op.wd, w) for op, w in zip([op for op in packed if op.wd is not None], before["wd"]))
     monkeypatch.setattr(ops.ConvOp, "bwd_dw", bwd_dw)
-    tr.step(cw.step_batch(ref, "cpu"))                                      # the next, clean step is taken (at the halved loss scale)
+    tr.step(sc.step_batch(ref, "cpu"))                                      # the next, clean step is taken (at the halved loss scale)
     assert float(tr.opt_state[7]) == 0.0 and float(tr.opt_state[0]) == 1.0 and not torch.equal(tr.p_flat, before["p"])
 
 
-def test_default_selection_is_unchanged_and_other_selections_are_refused(emu_installed):
+def test_default_selection_is_unchanged_and_other_selections_are_refused(emu_backend):
     from oracle.unet import TINY_CONFIG
     from svd_xtend_amd.lora import LoraConfig
     from svd_xtend_amd.train import Trainer, select_trainable
     from svd_xtend_amd.unet import UNetSpatioTemporalConditionModel
-    ref = cw.oracle_step(cw.CONV_AND_TEMPORAL)
+    ref = sc.oracle_step(cw.CONV_AND_TEMPORAL)
 
     def model():
         m = UNetSpatioTemporalConditionModel(**TINY_CONFIG)

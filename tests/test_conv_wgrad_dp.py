@@ -18,9 +18,9 @@ def _setup():
     for p in (ROOT, HERE):
         if p not in sys.path:
             sys.path.insert(0, p)
-    import conv_wgrad_checks as cw
+    import emul
     from svd_xtend_amd import kernels
-    kernels._set_backend_for_tests(cw.ConvWgradEmuBackend())
+    kernels._set_backend_for_tests(emul.EmuBackend())
 
 
 def _make(seed):

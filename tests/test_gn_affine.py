@@ -1,5 +1,5 @@
 """CPU (`-m "not gpu"`): the GroupNorm affine gradients -- svdx_gn_bwd_stats_affine with the kernel source executed by the simulator of
-tests/sim/ and with the emulation of tests/gn_affine_checks.py, against float64 autograd through F.group_norm (+ F.silu) under the
+tests/sim/ and with the emulation of tests/emul.py, against float64 autograd through F.group_norm (+ F.silu) under the
 per-channel bound of gn_affine_checks.bounds; the "@norm" selection rule; one optimizer step of the tiny topology on the emulation
 against the CPU oracle; the launch audit; the planted non-finite gradient."""
 import os
@@ -11,8 +11,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "sim"))
 
-import conv_wgrad_checks as cw  # noqa: E402
+import emul  # noqa: E402
 import gn_affine_checks as ga  # noqa: E402
+import selection_checks as sc  # noqa: E402
 from svd_xtend_amd import kernels as K  # noqa: E402
 
 
@@ -20,15 +21,6 @@ from svd_xtend_amd import kernels as K  # noqa: E402
 def sim():
     from backend import SimBackend
     return SimBackend()
-
-
-@pytest.fixture
-def emu_installed():
-    prev = K._backend
-    be = ga.GnAffineEmuBackend()
-    K._set_backend_for_tests(be)
-    yield be
-    K._set_backend_for_tests(prev)
 
 
 def test_case_table_and_block_count(sim):
@@ -50,7 +42,7 @@ def test_kernel_case_on_simulator(sim, name, dt):
 @pytest.mark.parametrize("name", [c.name for c in ga.CASES])
 def test_emulation_meets_the_same_reference(name):
     """SELF-CHECK of the test double: the emulation the step tests run on meets the float64 reference under the same bound"""
-    ga.sweep_case(ga.GnAffineEmuBackend(), "cpu", ga.BY_NAME[name], torch.float16)
+    ga.sweep_case(emul.EmuBackend(), "cpu", ga.BY_NAME[name], torch.float16)
 
 
 def test_zeros_or_a_dropped_sample_cannot_pass():
@@ -90,7 +82,7 @@ def _tiny():
 def test_norm_rule_selects_every_groupnorm_and_nothing_else():
     from svd_xtend_amd.train import select_trainable
     m = _tiny()
-    gn = ga.gn_names(m)
+    gn = sc.gn_names(m)
     assert len(gn) == 210                                  # 105 modules: 88 in the 22 ResNet pairs, 16 transformer `norm`s, conv_norm_out
     assert sorted(select_trainable(m, "@norm")) == gn
     assert sum(".norm1." in n or ".norm2." in n for n in gn) == 176 and sum(n.endswith(".norm.weight") for n in gn) == 16
@@ -112,7 +104,7 @@ def test_full_topology_has_105_groupnorms():
     assert len(select_trainable(m, "@norm")) == 210
 
 
-def test_norm_rule_is_ignored_under_lora_and_other_names_are_still_refused(emu_installed):
+def test_norm_rule_is_ignored_under_lora_and_other_names_are_still_refused(emu_backend):
     from svd_xtend_amd.lora import LoraConfig
     from svd_xtend_amd.train import Trainer, select_trainable
     lm = _tiny()
@@ -135,26 +127,26 @@ def test_norm_rule_is_ignored_under_lora_and_other_names_are_still_refused(emu_i
 # ---- the step: Trainer(trainable=...) on the emulation against the CPU oracle ------------------------------------------------------------
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
 @pytest.mark.parametrize("which", ga.SELECTIONS, ids=lambda w: w if isinstance(w, str) else "+".join(w))
-def test_step_matches_oracle(emu_installed, which, dt):
-    ref = ga.oracle_step(which)
-    got = cw.product_step(ref, which, ga.DT[dt], torch.device("cpu"))
+def test_step_matches_oracle(emu_backend, which, dt):
+    ref = sc.oracle_step(which)
+    got = sc.product_step(ref, which, ga.DT[dt], torch.device("cpu"))
     print(ga.assert_step_parity(f"emulation {which} {dt}", ref, got, bf16=dt == "bf16"))
     m = got["trainer"].model
     if which == "conv_norm_out":
         assert ref["names"] == ["conv_norm_out.bias", "conv_norm_out.weight"] and m._any_trainable and not m._sweep_needed
         assert all(mod.sv is None for kind, blk in m.steps if kind == "res" for mod in (blk.spatial_res_block, blk.temporal_res_block))
     else:
-        assert len([n for n in ref["names"] if n in set(ga.gn_names(m))]) == 210
+        assert len([n for n in ref["names"] if n in set(sc.gn_names(m))]) == 210
         assert all(mod.need_dx for kind, mod in m.steps[1:] if kind in ("res", "attn", "down", "up"))
 
 
-def test_conv_norm_out_alone_runs_one_data_gradient_and_one_statistics_launch(emu_installed):
-    ref = ga.oracle_step("conv_norm_out")
-    tr = cw.make_trainer(ref, "conv_norm_out", torch.float16, torch.device("cpu"))
+def test_conv_norm_out_alone_runs_one_data_gradient_and_one_statistics_launch(emu_backend):
+    ref = sc.oracle_step("conv_norm_out")
+    tr = sc.make_trainer(ref, "conv_norm_out", torch.float16, torch.device("cpu"))
     tr.zero_grad()
-    emu_installed.log = log = []
-    tr.forward_backward(**cw.step_batch(ref, "cpu"))
-    emu_installed.log = None
+    rec = emul.record(K._backend)
+    tr.forward_backward(**sc.step_batch(ref, "cpu"))
+    log = rec.names(depth=0)
     i = max(j for j, e in enumerate(log) if e == "svdx_edm_loss")
     bwd = [e for e in log[i + 1:] if e not in ("svdx_zero", "svdx_nchw_to_rows")]
     assert bwd == ["svdx_gemm", "svdx_gn_bwd_stats_affine", "svdx_ln_param_reduce_batch"], bwd
@@ -162,15 +154,15 @@ def test_conv_norm_out_alone_runs_one_data_gradient_and_one_statistics_launch(em
 
 @pytest.mark.parametrize("which", ["up_blocks.3.resnets.2.temporal_res_block.norm2", "up_blocks.3.resnets.2.spatial_res_block.norm1",
                                    "up_blocks.3.attentions.2.norm."])
-def test_a_trainable_tail_norm_stops_the_sweep_where_nothing_trains(emu_installed, which):
+def test_a_trainable_tail_norm_stops_the_sweep_where_nothing_trains(emu_backend, which):
     """need_dx == False corners: only one norm near the end of the UNet trains.  Its gradient matches the oracle; no svdx_gn_bwd_apply
     runs for it (statistics only), and the sweep computes nothing upstream of it."""
     import e2e_checks
-    ref = ga.oracle_step(which)
+    ref = sc.oracle_step(which)
     assert len(ref["names"]) == 2
-    emu_installed.log = log = []
-    got = cw.product_step(ref, which, torch.float16, torch.device("cpu"))
-    emu_installed.log = None
+    rec = emul.record(K._backend)
+    got = sc.product_step(ref, which, torch.float16, torch.device("cpu"))
+    log = rec.names(depth=0)
     for n in ref["names"]:
         assert e2e_checks.cosine(got["grads"][n], ref["grads"][n]) >= 0.9995, n
     m = got["trainer"].model
@@ -182,10 +174,10 @@ def test_a_trainable_tail_norm_stops_the_sweep_where_nothing_trains(emu_installe
     assert log[i:i + 2] == ["svdx_gn_bwd_stats_affine", "svdx_ln_param_reduce_batch"], log[i:i + 4]      # the sweep's flush: nothing between
 
 
-def test_two_sweeps_after_zero_grad_give_the_same_gradients(emu_installed):
-    ref = ga.oracle_step(ga.ALL_THREE)
-    tr = cw.make_trainer(ref, ga.ALL_THREE, torch.float16, torch.device("cpu"))
-    batch = cw.step_batch(ref, "cpu")
+def test_two_sweeps_after_zero_grad_give_the_same_gradients(emu_backend):
+    ref = sc.oracle_step(ga.ALL_THREE)
+    tr = sc.make_trainer(ref, ga.ALL_THREE, torch.float16, torch.device("cpu"))
+    batch = sc.step_batch(ref, "cpu")
     sweeps = []
     for _ in range(2):
         tr.zero_grad()
@@ -194,7 +186,7 @@ def test_two_sweeps_after_zero_grad_give_the_same_gradients(emu_installed):
         sweeps.append({n: p.grad.detach().clone() for n, p in tr.model.named_parameters() if p.requires_grad})
     differ = [n for n in sweeps[0] if not torch.equal(sweeps[0][n], sweeps[1][n])]
     assert not differ, differ[:8]
-    gn = set(ga.gn_names(tr.model))
+    gn = set(sc.gn_names(tr.model))
     # the affine slots are accumulated into (zeroed by the step, tested by svdx_check_finite_spans), never stored
     assert all(id(p) not in tr.rt.write_once for n, p in tr.model.named_parameters() if n in gn)
     spans = tr.finite_spans.tolist()
@@ -204,22 +196,25 @@ def test_two_sweeps_after_zero_grad_give_the_same_gradients(emu_installed):
 
 
 # ---- launch audit -----------------------------------------------------------------------------------------------------------------------
-def _step_launches(be, which):
-    ref = ga.oracle_step(ga.TEMPORAL_NORM)
-    tr = cw.make_trainer(ref, which, torch.float16, torch.device("cpu"))
-    be.log = log = []
-    tr.step(cw.step_batch(ref, "cpu"))
-    be.log = None
-    return log, tr
+def _step_launches(rec, which, depth=0):
+    """the entry names of one Trainer.step in the log `rec` of emul.record: depth 0 the launches, depth None every call"""
+    ref = sc.oracle_step(ga.TEMPORAL_NORM)
+    tr = sc.make_trainer(ref, which, torch.float16, torch.device("cpu"))
+    rec.clear()
+    rec.on = True
+    tr.step(sc.step_batch(ref, "cpu"))
+    rec.on = False
+    return rec.names(depth), tr
 
 
-def test_launch_audit(emu_installed):
+def test_launch_audit(emu_backend):
     """default set: no affine launch, the statistics launches as they were; with "@norm" every backward statistics launch has become the
     affine entry, one per GroupNorm module, and the reducing launch is still called once per sweep (its table grows, and the entry
     splits a table at SVDX_BATCH_MAX_JOBS jobs by itself)"""
     import collections
-    base, _ = _step_launches(emu_installed, "temporal_transformer_block")
-    norm, tr = _step_launches(emu_installed, ga.TEMPORAL_NORM)
+    rec = emul.record(K._backend)
+    base, _ = _step_launches(rec, "temporal_transformer_block")
+    norm, tr = _step_launches(rec, ga.TEMPORAL_NORM)
     cb, cn = collections.Counter(base), collections.Counter(norm)
     assert cb["svdx_gn_bwd_stats_affine"] == 0 and cb["svdx_gn_bwd_stats"] > 0
     n_gn = sum(isinstance(m, torch.nn.GroupNorm) for m in tr.model.modules())
@@ -231,11 +226,13 @@ def test_launch_audit(emu_installed):
     assert set(cn) - set(cb) == {"svdx_gn_bwd_stats_affine"}
 
 
-def test_default_set_issues_the_parents_launches(emu_installed):
-    """the default trainable set: the entry names of a step, in order, are a fixed list whose digest was recorded on the parent commit
-    with this same emulation wrapper"""
-    base, _ = _step_launches(emu_installed, "temporal_transformer_block")
-    again, _ = _step_launches(emu_installed, "temporal_transformer_block")
+def test_default_set_issues_the_parents_launches(emu_backend):
+    """the default trainable set: the entry names of a step, in order, are a fixed list whose digest was recorded on the parent commit.
+    The digest covers the calls at ALL depths of the recorder (it was taken by a logger that could not tell them apart); the launches
+    among them, depth 0, are counted in tests/test_emul_complete.py"""
+    rec = emul.record(K._backend)
+    base, _ = _step_launches(rec, "temporal_transformer_block", depth=None)
+    again, _ = _step_launches(rec, "temporal_transformer_block", depth=None)
     assert base == again and "svdx_gn_bwd_stats_affine" not in base
     import hashlib
     assert (len(base), hashlib.sha256("\n".join(base).encode()).hexdigest()) == ga.PARENT_DEFAULT_LAUNCHES, (len(base),)
@@ -243,12 +240,12 @@ def test_default_set_issues_the_parents_launches(emu_installed):
 
 # ---- non-finite gradient ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("which", [ga.TEMPORAL_NORM, "@norm"], ids=["temporal+norm", "norm"])
-def test_planted_nonfinite_norm_gradient_skips_the_step(emu_installed, monkeypatch, which):
+def test_planted_nonfinite_norm_gradient_skips_the_step(emu_backend, monkeypatch, which):
     """one inf in the dy of one norm's backward: the step is skipped and masters and moments keep every bit -- with write-once gradients
     beside the norms (svdx_check_finite_spans over the accumulated slots) and with the norms alone (the full pass)"""
     from svd_xtend_amd import ops
-    ref = ga.oracle_step(which)
-    tr = cw.make_trainer(ref, which, torch.float16, torch.device("cpu"))
+    ref = sc.oracle_step(which)
+    tr = sc.make_trainer(ref, which, torch.float16, torch.device("cpu"))
     target = tr.model.mid_block.resnets[0].temporal_res_block.gn2
     before = dict(p=tr.p_flat.clone(), m=tr.m_flat.clone(), v=tr.v_flat.clone())
     bwd, hit = ops.GroupNormOp.bwd, []
@@ -260,20 +257,20 @@ def test_planted_nonfinite_norm_gradient_skips_the_step(emu_installed, monkeypat
             hit.append(1)
         return bwd(self, rt, dy, x, *a, **k)
     monkeypatch.setattr(ops.GroupNormOp, "bwd", planted)
-    tr.step(cw.step_batch(ref, "cpu"))
+    tr.step(sc.step_batch(ref, "cpu"))
     assert hit and float(tr.opt_state[7]) == 1.0 and float(tr.opt_state[0]) == 0.0
     assert not torch.isfinite(tr.model.mid_block.resnets[0].temporal_res_block.norm2.weight.grad).all()
     assert torch.equal(tr.p_flat, before["p"]) and torch.equal(tr.m_flat, before["m"]) and torch.equal(tr.v_flat, before["v"])
     monkeypatch.setattr(ops.GroupNormOp, "bwd", bwd)
-    tr.step(cw.step_batch(ref, "cpu"))                                      # the next, clean step is taken (at the halved loss scale)
+    tr.step(sc.step_batch(ref, "cpu"))                                      # the next, clean step is taken (at the halved loss scale)
     assert float(tr.opt_state[7]) == 0.0 and float(tr.opt_state[0]) == 1.0 and not torch.equal(tr.p_flat, before["p"])
 
 
-def test_updated_affines_reach_the_next_forward(emu_installed):
+def test_updated_affines_reach_the_next_forward(emu_backend):
     """gamma / beta are read from the master: after an optimizer step the forward (and `reapply`, the re-made conv inputs) sees the new
     values with nothing to refresh -- pred_after of assert_parity covers the forward; here the master IS the flat buffer"""
-    ref = ga.oracle_step("@norm")
-    tr = cw.make_trainer(ref, "@norm", torch.float16, torch.device("cpu"))
+    ref = sc.oracle_step("@norm")
+    tr = sc.make_trainer(ref, "@norm", torch.float16, torch.device("cpu"))
     for p, off in zip(tr.params, tr.offsets):
         assert p.data.data_ptr() == tr.p_flat[off:].data_ptr()
     op = tr.model.mid_block.resnets[0].spatial_res_block.gn1

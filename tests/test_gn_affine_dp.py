@@ -19,16 +19,16 @@ def _setup():
     for p in (ROOT, HERE):
         if p not in sys.path:
             sys.path.insert(0, p)
-    import gn_affine_checks as ga
+    import emul
     from svd_xtend_amd import kernels
-    kernels._set_backend_for_tests(ga.GnAffineEmuBackend())
+    kernels._set_backend_for_tests(emul.EmuBackend())
 
 
 def _worker(rank, world, port, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.set_num_threads(2)
     _setup()
-    import gn_affine_checks as ga
+    import selection_checks as sc
     import test_conv_wgrad_dp as base
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from svd_xtend_amd.train import Trainer
@@ -44,7 +44,7 @@ def _worker(rank, world, port, out):
         res[overlap]["summed"] = tr.g_flat.clone()
         tr.optimizer_step()
         res[overlap]["p"] = tr.p_flat.clone()
-    gn = set(ga.gn_names(tr.model))
+    gn = set(sc.gn_names(tr.model))
     named = [(n, p) for n, p in tr.model.named_parameters() if p.requires_grad]
     assert [n for n, _ in named] == tr.names
     norm = [(n, o, p.numel()) for (n, p), o in zip(named, tr.offsets) if n in gn]

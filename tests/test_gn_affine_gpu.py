@@ -9,8 +9,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 
-import conv_wgrad_checks as cw  # noqa: E402
 import gn_affine_checks as ga  # noqa: E402
+import selection_checks as sc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -37,23 +37,23 @@ def test_kernel_case_on_device(hip, name, dt):
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
 @pytest.mark.parametrize("which", [ga.TEMPORAL_NORM, ga.ALL_THREE], ids=["temporal+norm", "temporal+conv+norm"])
 def test_step_matches_oracle(hip, which, dt):
-    ref = ga.oracle_step(which)
-    got = cw.product_step(ref, which, ga.DT[dt], torch.device("cuda"))
+    ref = sc.oracle_step(which)
+    got = sc.product_step(ref, which, ga.DT[dt], torch.device("cuda"))
     print(ga.assert_step_parity(f"device {which} {dt}", ref, got, bf16=dt == "bf16"))
 
 
 def test_conv_norm_out_alone_matches_oracle(hip):
-    ref = ga.oracle_step("conv_norm_out")
-    got = cw.product_step(ref, "conv_norm_out", torch.float16, torch.device("cuda"))
+    ref = sc.oracle_step("conv_norm_out")
+    got = sc.product_step(ref, "conv_norm_out", torch.float16, torch.device("cuda"))
     print(ga.assert_step_parity("device conv_norm_out f16", ref, got))
     m = got["trainer"].model
     assert m._any_trainable and not m._sweep_needed
 
 
 def test_a_second_sweep_after_zero_grad_gives_the_same_gradients_on_device(hip):
-    ref = ga.oracle_step(ga.ALL_THREE)
-    tr = cw.make_trainer(ref, ga.ALL_THREE, torch.float16, "cuda")
-    batch = cw.step_batch(ref, "cuda")
+    ref = sc.oracle_step(ga.ALL_THREE)
+    tr = sc.make_trainer(ref, ga.ALL_THREE, torch.float16, "cuda")
+    batch = sc.step_batch(ref, "cuda")
     sweeps = []
     for _ in range(2):
         tr.zero_grad()
@@ -62,26 +62,26 @@ def test_a_second_sweep_after_zero_grad_gives_the_same_gradients_on_device(hip):
         torch.cuda.synchronize()
         sweeps.append(tr.g_flat[:tr.n_flat].clone())
     assert torch.equal(sweeps[0], sweeps[1]), int((sweeps[0] != sweeps[1]).sum())
-    gn = set(ga.gn_names(tr.model))
+    gn = set(sc.gn_names(tr.model))
     assert all(float(p.grad.abs().max()) > 0 for n, p in tr.model.named_parameters() if n in gn)
 
 
 def test_captured_step_equals_eager_and_plan_replay_equals_graph_replay(hip):
     """three optimizer steps with trainable norms (and convolutions, whose re-made inputs read the updated affines): the captured step
     walks the eager trajectory bit for bit -- masters, moments, loss, optimizer state -- and the recorded launch plan replays to the same"""
-    ref = ga.oracle_step(ga.ALL_THREE)
-    eager = ga.run_mode(ref, ga.ALL_THREE, "eager")
-    graph = ga.run_mode(ref, ga.ALL_THREE, "graph")
-    plan = ga.run_mode(ref, ga.ALL_THREE, "plan")
+    ref = sc.oracle_step(ga.ALL_THREE)
+    eager = sc.run_mode(ref, ga.ALL_THREE, "eager")
+    graph = sc.run_mode(ref, ga.ALL_THREE, "graph")
+    plan = sc.run_mode(ref, ga.ALL_THREE, "plan")
     assert eager["state"][0] == 3.0
-    ga.assert_same_bits(eager, graph, "captured vs eager")
-    ga.assert_same_bits(graph, plan, "plan vs graph")
+    sc.assert_same_bits(eager, graph, "captured vs eager")
+    sc.assert_same_bits(graph, plan, "plan vs graph")
 
 
 def test_planted_nonfinite_norm_gradient_skips_the_step_on_device(hip, monkeypatch):
     from svd_xtend_amd import ops
-    ref = ga.oracle_step(ga.TEMPORAL_NORM)
-    tr = cw.make_trainer(ref, ga.TEMPORAL_NORM, torch.float16, "cuda")
+    ref = sc.oracle_step(ga.TEMPORAL_NORM)
+    tr = sc.make_trainer(ref, ga.TEMPORAL_NORM, torch.float16, "cuda")
     target = tr.model.mid_block.resnets[0].temporal_res_block.gn2
     before = dict(p=tr.p_flat.clone(), m=tr.m_flat.clone(), v=tr.v_flat.clone())
     bwd, hit = ops.GroupNormOp.bwd, []
@@ -93,7 +93,7 @@ def test_planted_nonfinite_norm_gradient_skips_the_step_on_device(hip, monkeypat
             hit.append(1)
         return bwd(self, rt, dy, x, *a, **k)
     monkeypatch.setattr(ops.GroupNormOp, "bwd", planted)
-    tr.step(cw.step_batch(ref, "cuda"))
+    tr.step(sc.step_batch(ref, "cuda"))
     torch.cuda.synchronize()
     assert hit and float(tr.opt_state[7]) == 1.0 and float(tr.opt_state[0]) == 0.0
     assert torch.equal(tr.p_flat, before["p"]) and torch.equal(tr.m_flat, before["m"]) and torch.equal(tr.v_flat, before["v"])

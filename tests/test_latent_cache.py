@@ -1,6 +1,6 @@
 """CPU (`-m "not gpu"`): the latent cache (svd_xtend_amd/latent_cache.py), its kernel svdx_latent_batch on the wave64 simulator, and
 `TrainLoop(latent_cache=...)` over the emulated kernels.  The kernel's result is DEFINED as the torch statements of
-tests/latent_cache_checks.py (`statements`): every comparison with them is `torch.equal`."""
+tests/emul.py (`latent_statements`, here `lc.statements`): every comparison with them is `torch.equal`."""
 import ctypes
 import os
 import subprocess
@@ -17,16 +17,6 @@ sys.path.insert(0, os.path.join(HERE, "sim"))
 import latent_cache_checks as lc  # noqa: E402
 
 T = 3
-
-
-@pytest.fixture
-def latent_emu():
-    """emul.EmuBackend + latent_batch (the `emu_backend` fixture of conftest.py knows nothing of the new entry)."""
-    from svd_xtend_amd import kernels
-    prev = kernels._backend
-    kernels._set_backend_for_tests(lc.LatentEmuBackend())
-    yield
-    kernels._set_backend_for_tests(prev)
 
 
 def towers(seed=0, grad_accum=1):
@@ -99,7 +89,7 @@ def test_argument_validation_without_device():
 
 
 # ---- 3. cache contents ----------------------------------------------------------------------------------------------------------
-def test_cache_contents_save_load_and_window(latent_emu, tmp_path):
+def test_cache_contents_save_load_and_window(emu_backend, tmp_path):
     from svd_xtend_amd.clip import encode_image
     from svd_xtend_amd.latent_cache import LatentCache
     from svd_xtend_amd.vae import AutoencoderKLTemporalDecoder
@@ -172,7 +162,7 @@ def recording(loop, forced_p=None):
 
 
 @pytest.mark.parametrize("B", [1, 2])
-def test_batch_from_cache_equals_the_statements(latent_emu, B):
+def test_batch_from_cache_equals_the_statements(emu_backend, B):
     from svd_xtend_amd.latent_cache import LatentCache
     from svd_xtend_amd.loop import BATCH_KEYS, TrainLoop
     tr, vae, enc = towers()
@@ -214,7 +204,7 @@ def test_batch_from_cache_equals_the_statements(latent_emu, B):
 
 
 # ---- 5. cached against uncached, same seed --------------------------------------------------------------------------------------
-def test_cached_loop_against_uncached_loop_same_seed(latent_emu):
+def test_cached_loop_against_uncached_loop_same_seed(emu_backend):
     from svd_xtend_amd.latent_cache import LatentCache
     from svd_xtend_amd.loop import TrainLoop
     tr, vae, enc = towers()
@@ -253,7 +243,7 @@ def test_cached_loop_against_uncached_loop_same_seed(latent_emu):
 
 
 # ---- 6. loop behaviour ----------------------------------------------------------------------------------------------------------
-def test_pipelined_cached_loop_equals_sequential_steps(latent_emu):
+def test_pipelined_cached_loop_equals_sequential_steps(emu_backend):
     """tests/test_train_loop.py::test_pipelined_loop_equals_sequential_steps over a cache: three steps, EMA on."""
     from svd_xtend_amd.latent_cache import LatentCache
     from svd_xtend_amd.loop import TrainLoop
@@ -283,7 +273,7 @@ def test_pipelined_cached_loop_equals_sequential_steps(latent_emu):
     assert all(l == l and l > 0 for l in out[0][0])
 
 
-def test_grad_accum_and_item_count(latent_emu):
+def test_grad_accum_and_item_count(emu_backend):
     from svd_xtend_amd.latent_cache import LatentCache
     from svd_xtend_amd.loop import TrainLoop
     tr, vae, enc = towers(grad_accum=2)
@@ -314,6 +304,7 @@ import torch
 import emul
 from svd_xtend_amd import kernels
 kernels._set_backend_for_tests(emul.EmuBackend())
+rec = emul.record(kernels._backend)
 import train_svd_amd as ex
 from svd_xtend_amd.loop import BATCH_KEYS, TrainLoop
 from svd_xtend_amd.train import Trainer
@@ -322,14 +313,14 @@ unet, vae, enc = ex.build_models(args, torch.device("cpu"), torch.float32)
 loop = TrainLoop(Trainer(unet, dtype=torch.float32, lr=1e-3), vae, enc, conditioning_dropout_prob=0.1, seed=11, use_graph=False)
 clip = torch.rand(1, 3, 3, 64, 64, generator=torch.Generator().manual_seed(5)) * 2 - 1
 b = loop.prepare_batch(clip)
-assert "svd_xtend_amd.latent_cache" not in sys.modules and not hasattr(kernels._backend, "latent_batch")
+assert "svd_xtend_amd.latent_cache" not in sys.modules and rec and "svdx_latent_batch" not in rec.names()
 torch.save({{k: b[k] for k in BATCH_KEYS}}, {out!r})
 """
 
 
-def test_default_loop_is_untouched_by_the_new_module(latent_emu, tmp_path):
-    """latent_cache=None: prepare_batch for a fixed seed gives the bits it gives in a process that never imports the new module (and
-    whose backend has no latent_batch)."""
+def test_default_loop_is_untouched_by_the_new_module(emu_backend, tmp_path):
+    """latent_cache=None: prepare_batch for a fixed seed gives the bits it gives in a process that never imports the new module and
+    never calls svdx_latent_batch (the recorder of tests/emul.py sees every call that process makes, and sees some)."""
     import svd_xtend_amd.latent_cache  # noqa: F401  -- imported here, never there
     from svd_xtend_amd.loop import BATCH_KEYS, TrainLoop
     out = str(tmp_path / "batch.pt")

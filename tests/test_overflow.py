@@ -27,7 +27,6 @@ for _p in (ROOT, HERE, os.path.join(HERE, "sim")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-import clip_checks as cc  # noqa: E402
 import emul  # noqa: E402
 import overflow_checks as oc  # noqa: E402
 from svd_xtend_amd import kernels as K  # noqa: E402
@@ -45,7 +44,7 @@ def sim():
 
 @pytest.fixture
 def emu():
-    return cc.ClipEmuBackend()
+    return emul.EmuBackend()
 
 
 def _ok(bad):
@@ -251,7 +250,7 @@ def test_two_ranks_skip_together_when_one_rank_overflows(tmp_path):
 
 
 # ---- 6. the tests bite: four planted faults ---------------------------------------------------------------------------------------------------
-class BlindLastColumns(cc.ClipEmuBackend):
+class BlindLastColumns(emul.EmuBackend):
     """the emulated gemm_tn ignores the last 8 columns of C for the flag"""
 
     def gemm_tn(self, A, B, C, R, N, Kd, lda, ldb, ldc, out_mode=K.OUT_F32_ADD, split_k=1, a_colsum=None, stages=0, found_inf=None):
@@ -260,7 +259,7 @@ class BlindLastColumns(cc.ClipEmuBackend):
             found_inf[0] = 1.0
 
 
-class TwinIgnoresSkip(cc.ClipEmuBackend):
+class TwinIgnoresSkip(emul.EmuBackend):
     """adamw_tiled ignores opt_state[7] for the transposed twin"""
 
     def adamw_tiled(self, p, g, m, v, tiles, n_tiles, lr, beta1, beta2, eps, wd, grad_mul, st, p_act, pt_act, param_mode=0):
@@ -280,7 +279,7 @@ def test_planted_fault_flag_blind_to_the_last_columns_fails_the_detector_sweep()
                        oc.tn_plant_store_f16(be, CPU, stages, shape)):
             assert bad and all("not raised" in b for b in bad), bad[:3]
             print(f"stages={stages}: {len(bad)} launches reported, e.g. {bad[0]}")
-    assert not oc.tn_plant_add(cc.ClipEmuBackend(), CPU, torch.float16, 0, oc.tn_shapes(0)[0])[0]
+    assert not oc.tn_plant_add(emul.EmuBackend(), CPU, torch.float16, 0, oc.tn_shapes(0)[0])[0]
 
 
 def test_planted_fault_dropped_finite_spans_row_fails_coverage_and_the_slot_test(monkeypatch, emu):

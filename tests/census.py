@@ -7,6 +7,7 @@ and judges every output against the float64 reference of tests/ref64.py with the
 passes around the step the same way (COND_CONFIGS: VAE encode / decode, the CLIP image path, the sampler's batch-2 forward, packing, EMA).
 `census(name)` also records the geometries beyond the two benchmarked (GEOM_EDGE, GEOM_GRID, GEOM_TINY); `geom_gpu_signatures()` is what
 the GPU runs of them: every signature of the edge geometries and one per dispatch class of the grid that nothing else reaches.
+`reach(signature)` is the extent in bytes of every tensor argument, `gemm_kernel_taken` the entry points' own conditions on it.
 
 Signature = (entry, ((argument name, value), ...)) in the order of `kernels.HipBackend`'s method.  A value is an int / float / bool / None,
 a `kernels.Gather`, a tuple of per-job tuples for the `*_batch` entries, or -- for a tensor -- ("T", dtype name, alias, table, n) where
@@ -201,7 +202,9 @@ def _grid():
 
 
 # GEOM_GRID: recorded host-only; a geometry another table already records goes under that table's name (one recording).  The grid
-# SAMPLES an unbounded domain: a geometry outside it may reach a dispatch class nothing runs.
+# SAMPLES an unbounded domain: a geometry outside it may reach a dispatch class nothing runs.  (How far an operand reaches in memory is
+# part of the class -- `reach_key` -- and pinned beyond the grid by tests/reach_checks.py: every kernel change and refusal at 2 GiB,
+# addressing up to 4 GiB plus one row.)
 GEOM_GRID = _grid()
 # the tiny topology at the edge geometries it admits: the emulation and the simulator on the CPU
 GEOM_TINY = {
@@ -212,8 +215,12 @@ GEOM_TINY = {
     "t_1x17x8x16": ("tiny", (1, 17, 8, 16), torch.float16, 0, {}),      # the first T beyond tsa_fwd
     "t_2x16x8x16": ("tiny", (2, 16, 8, 16), torch.float16, 0, {}),      # tsa_fwd at its limit T = 16 with the row vector grouped by B = 2
 }
+# GEOM_REACH: recorded host-only and never run as a whole.  Batch 4 of config 4 puts the widest activations (M = 921600 rows of 2560
+# columns) beyond 2^32 bytes: its census names the entries that get a 4 GiB case of their own (tests/reach_checks.py) and is checked for
+# launches the library would refuse (tests/test_census_geom.py).
+GEOM_REACH = {"r_4x25x72x128_full": ("svd", (4, 25, 72, 128), torch.float16, 0, {})}
 ALL_CONFIGS = dict(CONFIGS)
-for _t in (GEOM_EDGE, GEOM_GRID, GEOM_TINY):
+for _t in (GEOM_EDGE, GEOM_GRID, GEOM_TINY, GEOM_REACH):
     ALL_CONFIGS.update(_t)
 _CACHE = {}
 
@@ -477,13 +484,17 @@ def rounding_means(got, ref, dt):
     return RoundingMeans().add(got, ref, dt).means()
 
 
+def single_bound(dt, ref, S, k_acc, e, extra=None):
+    """the single-rounding bound of the error model, per element"""
+    bound = 0.5 * ulp_of(ref, dt) + (k_acc + e) * 2.0 ** -23 * S
+    return bound if extra is None else bound + extra
+
+
 def judge_single(res, label, got, ref, S, k_acc, e, rounding=True, extra=None):
     """single-rounding bound; appends (label, excess = worst error / bound, worst index) and, for 16-bit outputs, the rounding-mode
     means.  `extra`: a further documented rounding point, per element."""
     dt = got.dtype
-    bound = 0.5 * ulp_of(ref, dt) + (k_acc + e) * 2.0 ** -23 * S
-    if extra is not None:
-        bound = bound + extra
+    bound = single_bound(dt, ref, S, k_acc, e, extra)
     res.append((label,) + _worst(_ratio(got, ref, bound)))
     if rounding and dt in (torch.float16, torch.bfloat16):
         RoundingMeans().add(got, ref, dt).report(res, label)
@@ -695,6 +706,15 @@ def _launch(be, o, overrides=None):
     _sync(o.dev)
 
 
+PITCH_COPY_MAX = 1 << 28            # elements between the rows of C that run_gemm copies to compare; beyond: they are zero and stay zero
+
+
+def _all_zero_rows(t, step=1 << 26):
+    """whether every element of the (strided, integer-typed) matrix is zero, a bounded number of elements at a time"""
+    rows = max(1, step // max(t.shape[1], 1))
+    return not any(bool((t[r:r + rows] != 0).any()) for r in range(0, t.shape[0], rows))
+
+
 @runner("gemm")
 def run_gemm(be, o, a):
     M, N, Kd, dt = a["M"], a["N"], a["K"], o.dtype("A")
@@ -735,12 +755,14 @@ def run_gemm(be, o, a):
     pitch = None
     if mode != K.OUT_F32_SLAB and epi != K.EPI_GEGLU_BWD and a["ldc"] > N and M > 1:
         pitch = torch.as_strided(o["C"], (M - 1, a["ldc"] - N), (a["ldc"], 1), o["C"].storage_offset() + N)
-        pitch_before = pitch.clone()
+        pitch = pitch.view(torch.int16 if pitch.element_size() == 2 else torch.int32)
+        # a gap of gigabytes (tests/reach_checks.py) is not copied: it is all zero bytes before the launch and all zero bytes after it
+        pitch_before = pitch.clone() if pitch.numel() <= PITCH_COPY_MAX else None
+        same = pitch_before is not None or _all_zero_rows(pitch)
     _launch(be, o)
     res = []
     if pitch is not None:
-        same = bool((pitch.view(torch.int16 if pitch.element_size() == 2 else torch.int32) ==
-                     pitch_before.view(torch.int16 if pitch.element_size() == 2 else torch.int32)).all())
+        same = bool((pitch == pitch_before).all()) if pitch_before is not None else same and _all_zero_rows(pitch)
         res.append(("columns N..ldc of C untouched", 0.0 if same else float("inf"), ()))
     A = _v(o["A"], nsrc, g.cin, g.lda) if g is not None else _v(o["A"], M, Kd, a["lda"])
     B = _v(o["B"], N, Kd, a["ldb"])
@@ -992,12 +1014,15 @@ def run_timestep_embed(be, o, a):
     return [("out",) + _worst(_ratio(_v(o["out"], n, dim, dim), ref, bound))]
 
 
-def run_case(be, sig, dev=None, operands_out=None):
+def run_case(be, sig, dev=None, operands_out=None, seed_of=None):
     """Launch `sig` on backend `be` with operands rebuilt from the signature and judge every output: [(label, excess, worst index)],
-    excess = error / bound (<= 1 passes).  `be` may be a kernel_checks.Pair (its implementation under test is used)."""
+    excess = error / bound (<= 1 passes).  `be` may be a kernel_checks.Pair (its implementation under test is used).  `seed_of`: the
+    signature whose seed the operands take (two signatures that differ in a pitch only then hold the same values)."""
     be = getattr(be, "impl", be)
     dev = dev or ("cuda" if isinstance(be, K.HipBackend) and type(be).__name__ == "HipBackend" else "cpu")
     o = Operands(sig, dev)
+    if seed_of is not None:
+        o.gen.manual_seed(sig_seed(seed_of))
     if operands_out is not None:
         operands_out.append(o)                  # the caller wants the tensors of the launch as well (o["C"], ...)
     res = RUNNERS[sig[0]](be, o, sig_args(sig))
@@ -2200,10 +2225,104 @@ def feature_key(sig):
     return tuple(key)
 
 
+class _Declared(Exception):
+    pass
+
+
+class _DeclaredOperands(Operands):
+    """the declarations of a runner without its tensors: `alloc()` ends the runner"""
+
+    def alloc(self):
+        raise _Declared()
+
+
+_REACH = {}
+REACH_2G, REACH_4G = 1 << 31, 1 << 32
+TN_SPAN_MAX = 0x7ffffff0          # csrc/gemm_tn.hip: spans up to this value go through buffer descriptors
+
+
+def reach(sig):
+    """{tensor argument: extent in bytes} of a launch, as the entry computes it -- which is how the entry's runner declares its operands
+    (GEMM A over the gather's source rows with the gather's pitch, B = (N - 1) ldb + K, C / res / aux over M rows of their pitch, gemm_tn's A
+    and B over R rows, q / k / v / o over nb S rows of `ld`, ...).  Host only: nothing is allocated."""
+    if sig not in _REACH:
+        o = _DeclaredOperands(sig, "cpu")
+        try:
+            RUNNERS[sig[0]](None, o, sig_args(sig))
+            raise AssertionError(f"{sig[0]}: the runner ended without allocating")
+        except _Declared:
+            pass
+        _REACH[sig] = {n: ext * DT_OF[o.desc[n][1]].itemsize for n, (ext, _, _) in o.decls.items()}
+    return _REACH[sig]
+
+
+def reach_class(nbytes):
+    """0: below 2^31 bytes; 1: 2^31 and more; 2: 2^32 and more"""
+    return (nbytes >= REACH_2G) + (nbytes >= REACH_4G)
+
+
+_GEMM_IN, _GEMM_OUT = ("A", "B", "dual.0", "dual.1"), ("C", "res", "aux_in", "aux_out")
+
+
+def reach_key(sig):
+    """the reach classes the entry's code distinguishes.  `gemm`: A or B (svdx_gemm leaves the tile kernels for the 64-bit-pointer kernel,
+    the dual / GroupNorm / GEGLU forms refuse) and C, res or aux (the store path stays, its offsets grow); `gemm_tn`: A or B (buffer
+    descriptors or the flat staging); every other entry: its largest operand."""
+    if sig[0] not in RUNNERS:
+        return ()
+    r = reach(sig)
+    big = lambda names: reach_class(max([r[n] for n in names if n in r], default=0))
+    if sig[0] == "gemm":
+        return (("reach A/B", big(_GEMM_IN)), ("reach C/res/aux", big(_GEMM_OUT)))
+    if sig[0] == "gemm_tn":               # (svdx_gemm_tn's own line: spans beyond TN_SPAN_MAX, 16 bytes short of 2^31, take the flat staging)
+        span = max(r["A"], r["B"])
+        return (("reach A/B", (span > TN_SPAN_MAX) + (span >= REACH_4G)),)
+    return (("reach", big(r)),)
+
+
+def gemm_kernel_taken(sig):
+    """which code a `gemm` / `gemm_tn` / `gemm_tn_gather` / `tsa_fwd` launch takes, from the conditions of the entry points
+    (csrc/gemm_nt.hip gemm_entry, csrc/gemm_tn.hip svdx_gemm_tn / svdx_gemm_tn_gather, csrc/tsa.hip svdx_tsa_fwd): a kernel's name, or
+    "refused: ..." where the library returns an error before it launches anything."""
+    a = sig_args(sig)
+    if sig[0] == "gemm_tn_gather":              # (no runner of its own: tests/conv_wgrad_checks.py) the spans as svdx_gemm_tn_gather forms them
+        g = a["gather"]
+        src = a["R"] if g.mode == K.GATHER_TEMPORAL3 else g.n_img * (g.hi >> g.ups) * (g.wi >> g.ups)
+        if max(((a["R"] - 1) * a["lda"] + a["N"]) * 2, ((src - 1) * g.lda + g.cin) * 2) > TN_SPAN_MAX:
+            return "refused: svdx_gemm_tn_gather: operands of 2 GiB and more are not supported"
+        return "gemm_tn kernel, gathered, buffer descriptors"
+    if sig[0] not in ("gemm", "gemm_tn", "tsa_fwd"):
+        return None
+    r = reach(sig)
+    if sig[0] == "gemm":
+        flat = r["A"] >= REACH_2G or r["B"] >= REACH_2G
+        if a["dual"] is not None and (flat or r["dual.0"] >= REACH_2G or r["dual.1"] >= REACH_2G):
+            return "refused: svdx_gemm_dual: operands too large for the buffer-addressed kernel"
+        if a["variant"] >= 2 and not flat:
+            return "tile kernel (buffer descriptors)"
+        if a["epilogue"] != K.EPI_NONE:
+            return "refused: svdx_gemm: fused epilogue unavailable (buffer too large for variant 4)"
+        if a["gn"] is not None:
+            return "refused: svdx_gemm_gn: statistics unavailable (buffer too large for variant 4)"
+        return "gemm_kernel (64-bit pointers)"
+    if sig[0] == "gemm_tn":
+        buf = r["A"] <= TN_SPAN_MAX and r["B"] <= TN_SPAN_MAX and not (a["stages"] & K.TN_FLAT)
+        return "gemm_tn kernel, buffer descriptors" if buf else "gemm_tn kernel, flat staging"
+    if a["B"] * a["T"] * a["HW"] * 3 * a["C"] * 2 >= REACH_2G:
+        return "refused: svdx_tsa_fwd: activation too large for 32-bit buffer offsets"
+    return "tsa_fwd kernel"
+
+
+
 def dispatch_class(sig):
-    """What decides which code a launch runs, without its extents: the entry, the dtypes of its tensors, every flag argument; for `gemm`
-    also the tile it resolves to, whether K is split, the gather's kind, fused GroupNorm statistics, which epilogue operands are there,
-    and N and K (the weight's shape: the tile rules and the K loop depend on them; M is what the geometry scales)."""
+    """What decides which code a launch runs: the entry, the dtypes of its tensors, every flag argument; for `gemm` also the tile it
+    resolves to, whether K is split, the gather's kind, fused GroupNorm statistics, which epilogue operands are there, and N and K (the
+    weight's shape: the tile rules and the K loop depend on them; M is what the geometry scales); and how far its operands reach in memory
+    (`reach_key`: below 2^31 bytes, 2^31 and more, 2^32 and more)."""
+    return _dispatch_class(sig) + reach_key(sig)
+
+
+def _dispatch_class(sig):
     entry, kv = sig
     a = dict(kv)
     key = [entry]
@@ -2249,7 +2368,8 @@ def sig_rows(sig):
 def geom_gpu_signatures():
     """{part name: Counter[signature]} of what tests/test_census_geom_gpu.py runs: every signature of the GEOM_EDGE geometries (less
     what GEOM_EDGE_MINUS says runs already) and, as part "grid", one signature for every dispatch class of GEOM_GRID that neither those
-    nor the step's own configurations (STEP_GPU) reach: the one with the fewest rows -- a class only large row counts reach runs there."""
+    nor the step's own configurations (STEP_GPU) reach: the one with the fewest rows -- a class only large row counts reach runs there;
+    those of them with an operand of 2^31 bytes or more form the part "grid_reach"."""
     if "geom_gpu" in _CACHE:
         return _CACHE["geom_gpu"]
     parts = collections.OrderedDict()
@@ -2265,7 +2385,9 @@ def geom_gpu_signatures():
                 key = (sig_rows(s), repr(s))
                 if cls not in best or key < best[cls][0]:
                     best[cls] = (key, s)
-    parts["grid"] = collections.Counter({s: 1 for _, s in best.values()})
+    # (the classes that differ from another by their reach alone -- batch 2 of config 4 at its real shape, gigabytes each -- as a part of their own)
+    parts["grid"] = collections.Counter({s: 1 for _, s in best.values() if not any(v for _, v in reach_key(s))})
+    parts["grid_reach"] = collections.Counter({s: 1 for _, s in best.values() if any(v for _, v in reach_key(s))})
     _CACHE["geom_gpu"] = parts
     return parts
 

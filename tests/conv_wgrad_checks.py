@@ -162,13 +162,27 @@ def banded(fill: torch.Tensor, dev):
 
 def bands_intact(flats) -> None:
     for name, flat in flats.items():
-        f = flat.cpu().float()
-        assert bool((f[:GUARD] == SENTINEL).all()) and bool((f[-GUARD:] == SENTINEL).all()), f"{name}: guard band written"
+        lo, hi = flat[:GUARD].cpu().float(), flat[-GUARD:].cpu().float()            # (the bands alone: a pitched buffer holds gigabytes between them)
+        assert bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all()), f"{name}: guard band written"
 
 
-def run_case(be, dev, c: Case, dt: torch.dtype, split_k: int, store: bool, slab: bool = True, stages: int = 0, verbose: bool = False):
+def pitched(fill: torch.Tensor, ld: int, dev):
+    """the rows of `fill` at a pitch of `ld` elements inside a zeroed, sentinel-banded flat buffer on `dev` (allocated there: only the
+    rows are touched): (flat, strided view of fill's shape)"""
+    rows, cols = fill.shape
+    n = (rows - 1) * ld + cols
+    flat = torch.zeros(2 * GUARD + n, dtype=fill.dtype, device=dev)
+    flat[:GUARD] = SENTINEL
+    flat[-GUARD:] = SENTINEL
+    view = torch.as_strided(flat, (rows, cols), (ld, 1), GUARD)
+    view.copy_(fill.to(dev))
+    return flat, view
+
+
+def run_case(be, dev, c: Case, dt: torch.dtype, split_k: int, store: bool, slab: bool = True, stages: int = 0, verbose: bool = False, ld_dy: int = 0):
     """svdx_gemm_tn_gather + svdx_conv_wgrad_finalize of one case on `dev` against the float64 reference, per element; every buffer
-    between guard bands, the operands unchanged.  slab=False (split_k 1): the kernel's own store mode (SVDX_OUT_F32) feeds the finalize,
+    between guard bands, the operands unchanged.  ld_dy: the pitch of dY's rows where it is not cout_p (tests/reach_checks.py).
+    slab=False (split_k 1): the kernel's own store mode (SVDX_OUT_F32) feeds the finalize,
     its column sums accumulate into a zeroed row, and its non-finite flag stays down.  -> worst error / bound (weight, bias)."""
     x, dy, c0_w, c0_b, ref = case_reference(c, dt)
     taps, R, N, Kd = taps_of(c), rows_of(c), c.cout_p, taps_of(c) * c.cin_p
@@ -180,13 +194,13 @@ def run_case(be, dev, c: Case, dt: torch.dtype, split_k: int, store: bool, slab:
                     ("cs", torch.full((split_k, N), nan) if slab else torch.zeros(1, N)),
                     ("w_grad", torch.full_like(c0_w, nan) if store else c0_w), ("b_grad", torch.full_like(c0_b, nan) if store else c0_b),
                     ("found", torch.zeros(4))):
-        flats[name], dv[name] = banded(t, dev)
+        flats[name], dv[name] = pitched(t, ld_dy, dev) if (name == "dy" and ld_dy) else banded(t, dev)
     g = gather_of(c, c.cin_p, c.cin_p)
     if slab:
-        be.gemm_tn_gather(dv["dy"], dv["x"], dv["slabs"], R, N, c.cout_p, Kd, g, out_mode=K.OUT_F32_SLAB, split_k=split_k, a_colsum=dv["cs"], stages=stages)
+        be.gemm_tn_gather(dv["dy"], dv["x"], dv["slabs"], R, N, ld_dy or c.cout_p, Kd, g, out_mode=K.OUT_F32_SLAB, split_k=split_k, a_colsum=dv["cs"], stages=stages)
     else:
         assert split_k == 1
-        be.gemm_tn_gather(dv["dy"], dv["x"], dv["slabs"], R, N, c.cout_p, Kd, g, out_mode=K.OUT_F32, a_colsum=dv["cs"], stages=stages, found_inf=dv["found"][0:1])
+        be.gemm_tn_gather(dv["dy"], dv["x"], dv["slabs"], R, N, ld_dy or c.cout_p, Kd, g, out_mode=K.OUT_F32, a_colsum=dv["cs"], stages=stages, found_inf=dv["found"][0:1])
     be.conv_wgrad_finalize(dv["slabs"], split_k, N * Kd, Kd, dv["w_grad"], c.cout, c.cin, c.cin_p, taps, alpha=c.alpha, store=store,
                            colsum_slabs=dv["cs"], colsum_ld=N, b_grad=dv["b_grad"], found_inf=dv["found"][1:2])
     if str(dev) != "cpu":

@@ -20,6 +20,13 @@ class SimBackend(K.HipBackend):
         self.n_calls = 0
         self.launch_log = None
 
+    def range_reports(self) -> int:
+        """buffer accesses so far whose range check depended on the scalar offset (sim_rt.cpp counts every one, prints the first five)"""
+        import ctypes
+        fn = self.lib.svdx_sim_range_reports
+        fn.restype = ctypes.c_long
+        return int(fn())
+
     @staticmethod
     def _stream():
         return None

@@ -458,6 +458,11 @@ void sim_dma(char* lds_dst, const void* src, int size) {
 
 void sim_waitcnt_vm(int n) { land(g_run->cur, (size_t)n); }
 
+// buffer accesses whose range check depended on the scalar offset, since the library was loaded (printed: the first five); tests read it
+// before and after a case (backend.SimBackend.range_reports)
+static std::atomic<long> g_range_reports{0};
+extern "C" long svdx_sim_range_reports(void) { return g_range_reports.load(); }
+
 const char* sim_buffer_addr(const SimRsrc& rs, int voffset, int soffset, int imm, int size) {
     const uint64_t checked = (uint64_t)(uint32_t)voffset + (uint32_t)imm;
     const uint64_t full = checked + (uint32_t)soffset;
@@ -465,8 +470,7 @@ const char* sim_buffer_addr(const SimRsrc& rs, int voffset, int soffset, int imm
     const bool oob_full = full + size > rs.num_records;
     if (oob_checked != oob_full) {
         // the scalar offset decides whether the access is in range: the two readings of the raw-buffer rule disagree here
-        static std::atomic<int> warned{0};
-        if (warned.fetch_add(1) < 5) fprintf(stderr, "svdx-sim: buffer access whose range check depends on the scalar offset (voffset %d soffset %d records %u)\n", voffset, soffset, rs.num_records);
+        if (g_range_reports.fetch_add(1) < 5) fprintf(stderr, "svdx-sim: buffer access whose range check depends on the scalar offset (voffset %d soffset %d records %u)\n", voffset, soffset, rs.num_records);
     }
     if (oob_checked || oob_full) return nullptr;
     return rs.base + full;

@@ -4,7 +4,9 @@ tiny topology at the edge geometries through the emulation and through the HIP s
 batch sizes its time-context ordering cannot serve, and the checker against faults planted at edge signatures.
 
 GEOM_GRID samples an unbounded domain (any multiple of 8 for the latent's sides, any frame count, any batch size): a geometry outside
-it may still reach a dispatch class that nothing runs."""
+it may still reach a dispatch class that nothing runs.  How far the operands reach in memory is part of the class: the signatures of the
+grid and of GEOM_REACH with an operand of 2^31 bytes or more are tabulated with the kernel they take, none of them is one the library
+would refuse, and each of the grid's runs on the GPU at its own reach; tests/test_reach.py pins the line itself at small shapes."""
 import collections
 import os
 import sys
@@ -93,6 +95,82 @@ def test_gpu_signatures_reach_every_dispatch_class_of_the_grid():
     assert S == {64, 16, 4, 1}, S
     assert {census.sig_args(s)["S"] for s in parts["e_1x14x24x40"] if s[0] == "attn_fwd"} == {960, 240, 60, 15}
     assert any(s[0] == "tattn_fwd" and census.sig_args(s)["HW"] == 1 for s in parts["e_1x1x8x8"])
+
+
+# ---- how far the operands reach ------------------------------------------------------------------------------------------------------------
+def _quoted(entry, **kw):
+    """whether some signature of batch 2 of config 4 (full and LoRA) has these arguments"""
+    return [s for n in ("g_2x25x72x128_full", "g_2x25x72x128_lora") for s in census.census(n)
+            if s[0] == entry and all(census.sig_args(s)[k] == v for k, v in kw.items())]
+
+
+def _reaching():
+    """[(geometry, signature)] of the grid and GEOM_REACH with an operand of 2^31 bytes or more, each signature once"""
+    out, seen = [], set()
+    for n in list(census.GEOM_GRID) + list(census.GEOM_REACH):
+        for s in sorted(census.census(n), key=repr):
+            if s[0] in census.RUNNERS and s not in seen and max(census.reach(s).values(), default=0) >= census.REACH_2G:
+                seen.add(s)
+                out.append((n, s))
+    return out
+
+
+def test_signatures_that_reach_2_gib_and_the_kernel_they_take():
+    """(the table profiles/reach_gpu.txt keeps)"""
+    rows = _reaching()
+    print(f"{len(rows)} signatures of the grid and of {list(census.GEOM_REACH)} with an operand of 2^31 bytes or more:")
+    for n, s in rows:
+        big = {k: f"{v / 2 ** 30:.2f} GiB" for k, v in census.reach(s).items() if v >= census.REACH_2G}
+        print(f"  {n}: {census.reach_key(s)} {big} -> {census.gemm_kernel_taken(s) or 'the same kernel'}: {census.sig_str(s, 260)}")
+    taken = {s: census.gemm_kernel_taken(s) for _, s in rows}
+    dgrad = _quoted("gemm", M=460800, N=320, K=2560, variant=16)
+    assert dgrad and all(census.reach(s)["A"] >= census.REACH_2G and taken[s] == "gemm_kernel (64-bit pointers)" for s in dgrad)
+    for epi, N, aux in ((K.EPI_GEGLU_FWD, 2560, "aux_out"), (K.EPI_GEGLU_BWD, 1280, "aux_in")):
+        fused = _quoted("gemm", M=460800, N=N, K=320, variant=26, epilogue=epi)
+        assert fused and all(taken[s] == "tile kernel (buffer descriptors)" and census.reach(s)["C"] >= census.REACH_2G and
+                             census.reach(s)["A"] < census.REACH_2G and aux in census.reach(s) for s in fused), (epi, fused)
+    tn = _quoted("gemm_tn", R=460800, N=2560, K=320, lda=2560)
+    assert tn and all(census.reach(s)["A"] >= census.REACH_2G and taken[s] == "gemm_tn kernel, flat staging" for s in tn)
+    # GEOM_REACH is what reaches 2^32 bytes: through both GEMM entries
+    assert {s[0] for n, s in rows if n in census.GEOM_REACH and max(census.reach(s).values()) >= census.REACH_4G} == {"gemm", "gemm_tn"}
+    assert not any(max(census.reach(s).values()) >= census.REACH_4G for n, s in rows if n in census.GEOM_GRID)
+
+
+def test_no_recorded_launch_is_one_the_library_would_refuse():
+    """from the conditions of the entry points (census.gemm_kernel_taken): the dual, GroupNorm-statistics and fused-GEGLU forms of svdx_gemm
+    with A or B of 2 GiB, svdx_tsa_fwd and svdx_gemm_tn_gather beyond their limits.  The host's own fallbacks (ops.gemm_act's `gn_fits`, the
+    unfused path of unet.py's temporal block) are why none is recorded."""
+    n_judged, refused = 0, []
+    for n in list(census.GEOM_GRID) + list(census.GEOM_REACH):
+        for s in census.census(n):
+            verdict = census.gemm_kernel_taken(s) if s[0] in ("gemm", "gemm_tn", "gemm_tn_gather", "tsa_fwd") else None
+            n_judged += verdict is not None
+            if verdict is not None and verdict.startswith("refused"):
+                refused.append(f"{n}: {verdict}: {census.sig_str(s, 300)}")
+    print(f"{n_judged} recorded gemm / gemm_tn / gemm_tn_gather / tsa_fwd signatures judged")
+    assert n_judged > 1000 and not refused, "\n".join(refused[:20])
+    # the conditions themselves, at the line: one step below is served, the line is refused
+    sig = _quoted("gemm", M=460800, N=320, K=2560, variant=16)[0]
+
+    def with_args(s, **kw):
+        return (s[0], tuple((k, kw.get(k, v)) for k, v in s[1]))
+    assert census.gemm_kernel_taken(with_args(sig, M=419430)) == "tile kernel (buffer descriptors)"          # 419430 * 2560 * 2 = 2^31 - 2560
+    assert census.gemm_kernel_taken(with_args(sig, M=419431)) == "gemm_kernel (64-bit pointers)"
+    assert census.gemm_kernel_taken(with_args(sig, M=419431, gn=(("T", "f32", None, None, None), 1, 32))).startswith("refused: svdx_gemm_gn")
+    assert census.gemm_kernel_taken(with_args(sig, M=419431, epilogue=K.EPI_GEGLU_FWD, aux_dim=160)).startswith("refused: svdx_gemm: fused")
+
+
+def test_every_reach_class_of_the_grid_runs_on_the_gpu():
+    """a grid signature with an operand of 2^31 bytes or more takes other code than the signature of its class with the fewest rows: the
+    GPU selection (census.geom_gpu_signatures, census.STEP_GPU) holds a signature of the same class AND the same reach for each.  Reach
+    is computed here from census.reach_key, not read off the dispatch class."""
+    base = lambda s: (census._dispatch_class(s), census.reach_key(s))
+    run = {base(s) for c in census.geom_gpu_signatures().values() for s in c} | {base(s) for n in census.STEP_GPU for s in census.census(n)}
+    rows = [(n, s) for n, s in _reaching() if n in census.GEOM_GRID]
+    assert len(rows) >= 7 and {s[0] for _, s in rows} == {"gemm", "gemm_tn"}
+    missing = [f"{n}: {census.reach_key(s)}: {census.sig_str(s, 300)}" for n, s in rows if base(s) not in run]
+    assert not missing, "grid signatures whose reach no GPU part runs:\n" + "\n".join(missing)
+    assert all(census.dispatch_class(s)[-len(census.reach_key(s)):] == census.reach_key(s) for _, s in rows)
 
 
 @pytest.mark.parametrize("name", sorted(census.GEOM_EDGE) + sorted(census.GEOM_TINY) + ["grid"])

@@ -4,7 +4,9 @@ pixel per frame --, a 3x5 deepest level, batches of 2 and 3, 1, 16 and 17 frames
 geometry grid (GEOM_GRID) that neither those nor the step's own configurations reach, through HipBackend on operands rebuilt from the
 signature, judged element by element against the float64 reference (tests/ref64.py) computed on the device.  The bounds are the census's
 derived ones.  tests/test_census_geom.py asserts on the CPU that this selection reaches every dispatch class of the grid; the grid
-samples an unbounded domain, so a geometry outside it may still reach a class that nothing runs.
+samples an unbounded domain, so a geometry outside it may still reach a class that nothing runs.  The dispatch class holds how far the
+operands reach in memory (census.reach_key): batch 2 of config 4 puts A, or C and the GEGLU operand, of four GEMM classes and A of one
+gemm_tn class beyond 2^31 bytes, where svdx_gemm / svdx_gemm_tn take other code; those run here at their real shape (M = 460800).
 
 The host-only recording of the geometries sits in a module-scoped fixture; the signatures of a part are dealt into pieces of about
 equal cost so that each test takes a few seconds.  profiles/census_geom_gpu.txt has what was measured."""
@@ -20,9 +22,10 @@ from svd_xtend_amd import kernels as K
 pytestmark = pytest.mark.gpu
 
 # part -> pieces.  A signature costs about 12 ms whatever it is (operands, launch, judging) plus its float64 reference, which the cost
-# model of `_deal` puts at 5e11 units a second: the pieces come to 2 - 3 s each (profiles/census_geom_gpu.txt)
+# model of `_deal` puts at 5e11 units a second: the pieces come to 2 - 3 s each (profiles/census_geom_gpu.txt); the seven signatures of
+# "grid_reach" (M = 460800, operands of 2.2 GiB) get a piece each (profiles/reach_gpu.txt)
 PIECES = collections.OrderedDict([("e_1x1x8x8", 2), ("e_3x5x8x24", 4), ("e_1x14x24x40", 3), ("e_2x16x16x8", 7), ("e_1x17x16x24", 4),
-                                  ("e_2x14x40x64", 3), ("grid", 13)])
+                                  ("e_2x14x40x64", 3), ("grid", 13), ("grid_reach", 7)])
 CASES = [(name, i, k) for name, k in PIECES.items() for i in range(k)]
 _SEEN = {}
 _WORST = collections.defaultdict(float)
